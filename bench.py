@@ -8,6 +8,17 @@ fixed ("weak" scaling): when the driver already launched the ranks (WORLD_SIZE i
 rank joins; a bare `python bench.py --gpus N` spawns `torch.distributed.run` itself (a child process,
 started before anything touches the GPU) and exits with its status.  --mode infer measures configs[1].
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the line (with the
+`roofline` of the entry assumed to dominate, timed inside the K steps).  `--dump-outputs DIR` then writes arrays as
+DIR/<name>.npy (float32) by which two builds can be compared output for output, and leaves the timed steps as they
+are.  Images, masks, initial weights and the RoPE rescale draws are seeded.  --mode infer: `pred_masks` (a fixed
+sample) and `pred_iou` of the last timed step.  Training: after the timed steps the same step function runs twice more,
+untimed, from the seeded initial state: `step1_loss`, `step1_pred_masks` (a fixed sample), `step1_pred_iou`,
+`step1_params` (4096 elements of every parameter after the first update) and `step2_loss`.  The timed training steps'
+own outputs do not repeat from run to run (see `replay` in main) and are not written.
+Everything below that takes a run of its own -- the profiling pass behind `breakdown` (which also picks the roofline
+entry), `infer` / `infer_2048` / `c1`, every `cpu_baseline` -- is measured only with `--full`.
+
 `roofline`: the dominant C-ABI entry point of the step (largest summed GPU time in an untimed profiling
 pass) is timed live with HIP events on its launch stream around every call inside the timed region;
 `achieved` = its ALGORITHMIC work (tools/costs.py, from the call arguments) / that time.
@@ -308,6 +319,30 @@ def c1_plumbing(dev, cpu_iters, steps=10, warmup=2):
     return out
 
 
+# ------------------------------------------------------------------------------------ output dump
+DUMP_MAX_ELEMS = 4 << 20        # per array: 16 MB of float32, the whole dump stays far below 64 MB
+
+
+def _sample(t, n):
+    """`t` flattened when it has at most `n` elements, else a fixed sample of n of them (indices seeded by the size)."""
+    t = t.reshape(-1)
+    if t.numel() <= n:
+        return t.float()
+    import numpy as np
+    idx = np.sort(np.random.default_rng(t.numel()).integers(0, t.numel(), n))
+    return t[torch.from_numpy(idx).to(t.device)].float()
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of the last timed step as <path>/<name>.npy, float32."""
+    import numpy as np
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(path / f"{name}.npy", _sample(t, DUMP_MAX_ELEMS).cpu().numpy().astype(np.float32))
+    log(f"wrote {sorted(arrays)} to {path}")
+
+
 # ------------------------------------------------------------------------------------ launcher
 def _free_port():
     s = socket.socket()
@@ -353,6 +388,11 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 16 train / 8 infer)")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: per-class breakdown pass, inference lines (configs[1], "
+                         "[4], [0]) and the CPU baselines; the --no-* options below trim a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-iters", type=int, default=3, help="timed CPU-baseline iterations (after 1 warm-up)")
     ap.add_argument("--no-infer", action="store_true", help="skip the secondary inference lines (train mode)")
@@ -365,6 +405,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only: spawn / join the ranks over gloo (no GPU call), rank 0 reports the world")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_infer = args.no_breakdown = True
     if args.single_stream:
         os.environ["S3OD_BWD_SIDE"] = "0"
 
@@ -379,6 +421,7 @@ def main():
     if args.dry_run:
         return dry_run(args, world, rank, local)
     use_dist = world > 1 or args.ddp
+    torch.manual_seed(1000 + rank)      # the train forward draws its RoPE rescale from the CPU generator
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
     if use_dist and "RANK" not in os.environ:       # --ddp rehearsal without a launcher: a world of one
@@ -406,19 +449,44 @@ def main():
         crit = LossModule(FOCAL_IOU, full_mask_lambda=0.1, decay_rate=0.2)
         opt = FusedAdamW(reference_param_groups(model, 1e-5), weight_decay=0.05)
 
-        def step():
+        def step(keep=None):
             out = model(x)
             loss, _ = crit(out, {"images": x, "masks": masks}, 0)
             loss.backward()
             opt.step()
             model.zero_grad(set_to_none=False)
+            if keep is not None:
+                keep.update(loss=loss.detach(), pred_masks=out["pred_masks"].detach(), pred_iou=out["pred_iou"].detach())
             return loss
+
+        def replay(keep):
+            """--dump-outputs, after the timed steps: two more (untimed) steps of the same `step` from the seeded initial
+            state (weights and BatchNorm statistics regenerated from the seed, AdamW state dropped, RoPE draws reseeded).
+            Step 1 gives the forward and the loss on known weights; the weights after its update and the loss of step 2
+            carry the backward, the fused AdamW and the re-pack of the kernel-layout weights in float32.
+            The outputs of the timed steps themselves cannot serve: the backward accumulates with float atomics, the
+            bf16 forward turns the last-bit weight differences into rounding noise on every output one step later, and
+            the run on synthetic weights amplifies it -- after 13 steps two runs differ by 6e-3 of the largest logit,
+            after 33 steps by a quarter of the logits' rms and 5e-3 of the loss."""
+            fresh = DPTSegmentation(compute_dtype=args.dtype).state_dict()
+            model.load_state_dict(fresh)
+            opt.state.clear()
+            torch.manual_seed(2000 + rank)
+            first, second = {}, {}
+            step(first)
+            keep["step1_params"] = torch.cat([_sample(p.detach(), 4096) for _, p in sorted(model.named_parameters())])
+            step(second)
+            keep.update(step1_loss=first["loss"], step1_pred_masks=first["pred_masks"], step1_pred_iou=first["pred_iou"],
+                        step2_loss=second["loss"])
     else:
         model.eval()
 
-        def step():
+        def step(keep=None):
             with torch.no_grad():
-                return model(x)["pred_masks"]
+                out = model(x)
+            if keep is not None:
+                keep.update(pred_masks=out["pred_masks"], pred_iou=out["pred_iou"])
+            return out["pred_masks"]
 
     peak = PEAK_BF16 if args.dtype == "bf16" else PEAK_F32
     log(f"{args.mode} bs={B} {S}x{S} {args.dtype}: warm-up")
@@ -448,10 +516,11 @@ def main():
         sync.reset_timing(True)
     if use_dist:
         dist.barrier()
+    kept = {}
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        last = step(kept if args.dump_outputs and args.mode == "infer" and i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -472,6 +541,13 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             comm["comm_exposed_ms_max_over_ranks"], comm["allreduce_ms_per_step_max_over_ranks"] = \
                 round(float(t[0]), 3), round(float(t[1]), 3)
+    if args.dump_outputs:
+        if args.mode == "train":
+            kept.clear()
+            replay(kept)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, kept)
+        kept.clear()
     kms = sum(r[1] for r in rec) / max(len(rec), 1)
     work = sum(r[3] for r in rec) / max(len(rec), 1)
     kind = rec[0][2] if rec else "mfma"
@@ -505,8 +581,10 @@ def main():
                                          "gfx950-corrected, separate --pmc passes)",
                          "traffic_source": tr["source"] if tr else None,
                          "work_per_launch": work, "mean_launch_ms": round(kms, 4), "launches": len(rec),
-                         "note": "dominant C-ABI entry point by summed GPU time; HIP events on its launch stream around "
-                                 "every call in the timed region; work = algorithmic (tools/costs.py)"},
+                         "note": ("dominant C-ABI entry point by summed GPU time" if bd is not None else
+                                  "entry assumed dominant (measured only by the --full breakdown pass)") +
+                                 "; HIP events on its launch stream around every call in the timed region; work = "
+                                 "algorithmic (tools/costs.py)"},
             "mfma_frac_step": round(value / world * per_img / peak, 4) if per_img else None,
             "finite": ok,
         }
