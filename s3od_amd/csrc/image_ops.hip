@@ -24,15 +24,8 @@ DEV void cv_coef(int d, int ssize, int dsize, int& s0, int& s1, int& a0, int& a1
 }
 }  // namespace
 
-// one thread per destination pixel of the resized (new_h x new_w) image; writes normalised fp32
-// into the S x S canvas at (pad_h + y, pad_w + x).  The canvas must be pre-filled with the
-// normalised value of a zero pixel (kernel below).
-__global__ void preprocess_kernel(const unsigned char* __restrict__ img, int H0, int W0, int new_h, int new_w,
-                                  int pad_h, int pad_w, int S, float* __restrict__ out) {
-  int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= new_w || y >= new_h) return;
-  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-  int v[3];
+// resized-image pixel (x, y) of one uint8 HWC image: cv2 INTER_LINEAR fixed point, or the pixel itself when no resize
+DEV void pre_pixel(const unsigned char* __restrict__ img, int H0, int W0, int new_h, int new_w, int x, int y, int v[3]) {
   if (new_h == H0 && new_w == W0) {
     for (int c = 0; c < 3; c++) v[c] = img[((long)y * W0 + x) * 3 + c];
   } else {
@@ -49,11 +42,24 @@ __global__ void preprocess_kernel(const unsigned char* __restrict__ img, int H0,
       v[c] = o < 0 ? 0 : (o > 255 ? 255 : o);
     }
   }
-  for (int c = 0; c < 3; c++) {
-    float t = (float)v[c] / 255.0f;                  // float32 / python float -> float32 (numpy 2)
-    double d = ((double)t - mean[c]) / stdv[c];       // - float64 mean, / float64 std
-    out[((long)c * S + (pad_h + y)) * S + (pad_w + x)] = (float)d;
-  }
+}
+
+DEV float pre_norm(int v, int c) {
+  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
+  float t = (float)v / 255.0f;                      // float32 / python float -> float32 (numpy 2)
+  return (float)(((double)t - mean[c]) / stdv[c]);  // - float64 mean, / float64 std
+}
+
+// one thread per destination pixel of the resized (new_h x new_w) image; writes normalised fp32
+// into the S x S canvas at (pad_h + y, pad_w + x).  The canvas must be pre-filled with the
+// normalised value of a zero pixel (kernel below).
+__global__ void preprocess_kernel(const unsigned char* __restrict__ img, int H0, int W0, int new_h, int new_w,
+                                  int pad_h, int pad_w, int S, float* __restrict__ out) {
+  int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= new_w || y >= new_h) return;
+  int v[3];
+  pre_pixel(img, H0, W0, new_h, new_w, x, y, v);
+  for (int c = 0; c < 3; c++) out[((long)c * S + (pad_h + y)) * S + (pad_w + x)] = pre_norm(v[c], c);
 }
 
 __global__ void canvas_fill_kernel(float* out, int S) {
@@ -62,6 +68,71 @@ __global__ void canvas_fill_kernel(float* out, int S) {
   int c = i / ((long)S * S);
   const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
   out[i] = (float)((0.0 - mean[c]) / stdv[c]);
+}
+
+// ---------------------------------------------------------------- batched entries: descriptor tables
+// One descriptor per image; the tables are packed arrays in device memory (the host keeps a copy for the argument
+// checks).  include/s3od_hip.h carries these definitions; s3od_amd/infer_many.py mirrors them with ctypes.
+struct S3odPreDesc {   // 32 bytes
+  long img_off;        // @0  byte offset of the uint8 [H0][W0][3] image in the packed image buffer
+  int H0;              // @8  source height
+  int W0;              // @12 source width
+  int new_h;           // @16 resized height
+  int new_w;           // @20 resized width
+  int pad_h;           // @24 canvas row of the resized image's first row
+  int pad_w;           // @28 canvas column of the resized image's first column
+};
+struct S3odPostDesc {  // 56 bytes
+  long img_off;        // @0  byte offset of the uint8 [H0][W0][3] source image (read for the RGBA output only)
+  long mask_off;       // @8  offset in floats of this image's [planes][H0][W0] masks in the packed mask buffer
+  long rgba_off;       // @16 byte offset of this image's uint8 [H0][W0][4] RGBA in the packed RGBA buffer
+  long tmp_off;        // @24 offset in floats of this image's [planes][h][W0] scratch (two-pass branch only)
+  int pad_h;           // @32 first logit row of the crop
+  int pad_w;           // @36 first logit column of the crop
+  int h;               // @40 crop height
+  int w;               // @44 crop width
+  int H0;              // @48 output height
+  int W0;              // @52 output width
+};
+static_assert(sizeof(S3odPreDesc) == 32 && sizeof(S3odPostDesc) == 56, "descriptor layout is part of the C ABI");
+
+// one launch for B images: each thread writes 4 consecutive canvas pixels of one row for the 3 channels, either the
+// resampled image or the normalised zero pixel of the padding (no separate canvas fill).  block (64, 4).
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char* __restrict__ imgs,
+                                                               const S3odPreDesc* __restrict__ descs, int S, int vec,
+                                                               float* __restrict__ out) {
+  const int b = blockIdx.z;
+  const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y;
+  if (x0 >= S || y >= S) return;
+  const S3odPreDesc d = descs[b];
+  const unsigned char* img = imgs + d.img_off;
+  const int ry = y - d.pad_h;
+  const bool row_in = ry >= 0 && ry < d.new_h;
+  float o[3][4];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int rx = x0 + i - d.pad_w;
+    if (row_in && rx >= 0 && rx < d.new_w && x0 + i < S) {
+      int v[3];
+      pre_pixel(img, d.H0, d.W0, d.new_h, d.new_w, rx, ry, v);
+#pragma unroll
+      for (int c = 0; c < 3; c++) o[c][i] = pre_norm(v[c], c);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; c++) o[c][i] = pre_norm(0, c);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    float* dst = out + (((long)b * 3 + c) * S + y) * S + x0;
+    if (vec) {
+      *(float4*)dst = make_float4(o[c][0], o[c][1], o[c][2], o[c][3]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        if (x0 + i < S) dst[i] = o[c][i];
+    }
+  }
 }
 
 // ---------------------------------------------------------------- antialiased bilinear
@@ -118,6 +189,149 @@ __global__ void post_v_kernel(const float* __restrict__ tmp, int h, int H0, int 
   out[((long)c * H0 + y) * W0 + x] = acc;
 }
 
+// ---------------------------------------------------------------- batched post-processing
+// the tile kernel handles scale factors <= 2 on both axes (support <= 2 source pixels, at most 5 taps)
+static inline __host__ __device__ bool post_fused(int h, int w, int H0, int W0) {
+  return (float)h / (float)H0 <= 2.f && (float)w / (float)W0 <= 2.f;
+}
+
+constexpr int PT_W = 64, PT_H = 16, PT_TAPS = 6;           // output tile, taps kept per output row / column
+constexpr int PT_SW = 2 * PT_W + 8, PT_SH = 2 * PT_H + 8;  // source window: scale * (tile - 1) + 2 * support + 1 fits
+
+// plane p of image b -> mask index: every mask, or only the best one
+DEV int post_plane(int p, int planes, int NM, int best) { return planes == NM ? p : best; }
+
+// One 64 x 16 output tile of one mask plane per block (256 threads): the sigmoid of the source window is staged in
+// LDS, resampled horizontally into LDS and vertically from LDS; span and normalised weights are computed once per
+// tile column / row.  The block of the best plane also writes the RGBA tile (source RGB + truncated alpha).
+__global__ __launch_bounds__(256) void post_tile_kernel(const float* __restrict__ logits, int NM, int LH, int LW,
+                                                        const int* __restrict__ best, const unsigned char* __restrict__ imgs,
+                                                        const S3odPostDesc* __restrict__ descs, int planes,
+                                                        float* __restrict__ masks, unsigned char* __restrict__ rgba) {
+  __shared__ float src[PT_SH][PT_SW];
+  __shared__ float hbuf[PT_SH][PT_W];
+  __shared__ float hw[PT_TAPS][PT_W], vw[PT_TAPS][PT_H];
+  __shared__ int hmn[PT_W], hsz[PT_W], vmn[PT_H], vsz[PT_H];
+  const int b = blockIdx.z / planes, p = blockIdx.z % planes;
+  const S3odPostDesc d = descs[b];
+  if (!post_fused(d.h, d.w, d.H0, d.W0)) return;
+  const int ox0 = blockIdx.x * PT_W, oy0 = blockIdx.y * PT_H;
+  if (ox0 >= d.W0 || oy0 >= d.H0) return;
+  const int bi = best[b];
+  const int c = post_plane(p, planes, NM, bi);
+  const int tid = threadIdx.x, tx = tid & 63, ty = tid >> 6;
+
+  if (tid < PT_W) {
+    AASpan sp = aa_span(min(ox0 + tid, d.W0 - 1), d.w, d.W0);
+    hmn[tid] = sp.xmin;
+    hsz[tid] = max(min(sp.xsize, PT_TAPS), 0);
+    for (int j = 0; j < PT_TAPS; j++) hw[j][tid] = j < sp.xsize ? aa_weight(sp, j) : 0.f;
+  } else if (tid < PT_W + PT_H) {
+    const int r = tid - PT_W;
+    AASpan sp = aa_span(min(oy0 + r, d.H0 - 1), d.h, d.H0);
+    vmn[r] = sp.xmin;
+    vsz[r] = max(min(sp.xsize, PT_TAPS), 0);
+    for (int j = 0; j < PT_TAPS; j++) vw[j][r] = j < sp.xsize ? aa_weight(sp, j) : 0.f;
+  }
+  __syncthreads();
+  // spans are monotone in the output index: the window runs from the first span's start to the last span's end
+  const int sx_lo = hmn[0], sy_lo = vmn[0];
+  const int sw = min(hmn[PT_W - 1] + hsz[PT_W - 1] - sx_lo, PT_SW);
+  const int sh = min(vmn[PT_H - 1] + vsz[PT_H - 1] - sy_lo, PT_SH);
+
+  const float* lp = logits + (((long)b * NM + c) * LH + d.pad_h + sy_lo) * LW + d.pad_w + sx_lo;
+  for (int r = ty; r < sh; r += 4)
+    for (int q = tx; q < sw; q += 64) src[r][q] = 1.f / (1.f + expf(-lp[(long)r * LW + q]));
+  __syncthreads();
+
+  {
+    const int base = hmn[tx] - sx_lo, n = min(hsz[tx], PT_SW - base);
+    float wj[PT_TAPS];
+#pragma unroll
+    for (int j = 0; j < PT_TAPS; j++) wj[j] = hw[j][tx];
+    for (int r = ty; r < sh; r += 4) {
+      float acc = 0.f;
+#pragma unroll
+      for (int j = 0; j < PT_TAPS; j++)
+        if (j < n) acc += wj[j] * src[r][base + j];
+      hbuf[r][tx] = acc;
+    }
+  }
+  __syncthreads();
+
+  const int ox = ox0 + tx;
+  if (ox >= d.W0) return;
+  const bool alpha = rgba != nullptr && c == bi;
+#pragma unroll
+  for (int k = 0; k < PT_H / 4; k++) {
+    const int r = ty + 4 * k, oy = oy0 + r;
+    if (oy >= d.H0) break;
+    const int base = vmn[r] - sy_lo, n = min(vsz[r], PT_SH - base);
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < PT_TAPS; j++)
+      if (j < n) acc += vw[j][r] * hbuf[base + j][tx];
+    const long pix = (long)oy * d.W0 + ox;
+    masks[d.mask_off + (long)p * d.H0 * d.W0 + pix] = acc;
+    if (alpha) {
+      const unsigned char* s = imgs + d.img_off + pix * 3;
+      *(uchar4*)(rgba + d.rgba_off + pix * 4) = make_uchar4(s[0], s[1], s[2], (unsigned char)(acc * 255.f));
+    }
+  }
+}
+
+// batched form of post_h_kernel / post_v_kernel for the images the tile kernel leaves (a scale factor > 2)
+__global__ void post_h_batch_kernel(const float* __restrict__ logits, int NM, int LH, int LW, const int* __restrict__ best,
+                                    const S3odPostDesc* __restrict__ descs, int planes, float* __restrict__ tmp) {
+  const int b = blockIdx.z / planes, p = blockIdx.z % planes;
+  const S3odPostDesc d = descs[b];
+  if (post_fused(d.h, d.w, d.H0, d.W0)) return;
+  int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= d.W0 || y >= d.h) return;
+  const int c = post_plane(p, planes, NM, best[b]);
+  AASpan sp = aa_span(x, d.w, d.W0);
+  const float* row = logits + (((long)b * NM + c) * LH + (d.pad_h + y)) * LW + d.pad_w + sp.xmin;
+  float acc = 0.f;
+  for (int j = 0; j < sp.xsize; j++) acc += aa_weight(sp, j) * (1.f / (1.f + expf(-row[j])));
+  tmp[d.tmp_off + ((long)p * d.h + y) * d.W0 + x] = acc;
+}
+
+__global__ void post_v_batch_kernel(const float* __restrict__ tmp, int NM, const int* __restrict__ best,
+                                    const unsigned char* __restrict__ imgs, const S3odPostDesc* __restrict__ descs, int planes,
+                                    float* __restrict__ masks, unsigned char* __restrict__ rgba) {
+  const int b = blockIdx.z / planes, p = blockIdx.z % planes;
+  const S3odPostDesc d = descs[b];
+  if (post_fused(d.h, d.w, d.H0, d.W0)) return;
+  int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= d.W0 || y >= d.H0) return;
+  const int bi = best[b];
+  AASpan sp = aa_span(y, d.h, d.H0);
+  const float* col = tmp + d.tmp_off + ((long)p * d.h + sp.xmin) * d.W0 + x;
+  float acc = 0.f;
+  for (int j = 0; j < sp.xsize; j++) acc += aa_weight(sp, j) * col[(long)j * d.W0];
+  const long pix = (long)y * d.W0 + x;
+  masks[d.mask_off + (long)p * d.H0 * d.W0 + pix] = acc;
+  if (rgba != nullptr && post_plane(p, planes, NM, bi) == bi) {
+    const unsigned char* s = imgs + d.img_off + pix * 3;
+    *(uchar4*)(rgba + d.rgba_off + pix * 4) = make_uchar4(s[0], s[1], s[2], (unsigned char)(acc * 255.f));
+  }
+}
+
+// sigmoid of the IoU logits and the index of the first maximum (numpy.argmax), one thread per image
+__global__ void best_index_kernel(const float* __restrict__ iou_logits, int B, int NM, float* __restrict__ ious,
+                                  int* __restrict__ best) {
+  int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float bv = 0.f;
+  int bi = 0;
+  for (int c = 0; c < NM; c++) {
+    float s = 1.f / (1.f + expf(-iou_logits[(long)b * NM + c]));
+    ious[(long)b * NM + c] = s;
+    if (c == 0 || s > bv) { bv = s; bi = c; }
+  }
+  best[b] = bi;
+}
+
 extern "C" {
 
 // img: device uint8 [H0][W0][3]; out: fp32 [1][3][S][S]
@@ -141,6 +355,73 @@ int s3od_sigmoid_unpad_resize(const float* logits, int NM, int LH, int LW, int p
   hipLaunchKernelGGL(post_h_kernel, dim3(cdiv(W0, 256), h, NM), dim3(256), 0, st, logits, LH, LW, pad_h, pad_w, h, w, W0, tmp);
   hipLaunchKernelGGL(post_v_kernel, dim3(cdiv(W0, 256), H0, NM), dim3(256), 0, st, tmp, h, H0, W0, out);
   return s3od_check_launch("sigmoid_unpad_resize");
+}
+
+// imgs: device uint8, B HWC images packed at descs[b].img_off; descs / descs_host: the same S3odPreDesc[B] table in
+// device and in host memory (the host copy is read for the argument checks before the launch); out: fp32 [B][3][S][S]
+int s3od_preprocess_batch(const void* imgs, const void* descs, const void* descs_host, int B, int S, float* out, void* stream) {
+  S3OD_REQUIRE(B >= 1 && B <= 65535 && S >= 1 && descs_host != nullptr, "preprocess_batch: bad batch / canvas size");
+  const S3odPreDesc* hd = (const S3odPreDesc*)descs_host;
+  for (int b = 0; b < B; b++) {
+    S3OD_REQUIRE(hd[b].img_off >= 0 && hd[b].H0 > 0 && hd[b].W0 > 0 && hd[b].new_h > 0 && hd[b].new_w > 0,
+                 "preprocess_batch: image %d: bad size / offset", b);
+    S3OD_REQUIRE(hd[b].pad_h >= 0 && hd[b].pad_w >= 0 && hd[b].new_h + hd[b].pad_h <= S && hd[b].new_w + hd[b].pad_w <= S,
+                 "preprocess_batch: image %d: resized image does not fit the canvas", b);
+  }
+  const int vec = (S % 4 == 0) && ((uintptr_t)out % 16 == 0);
+  hipLaunchKernelGGL(preprocess_batch_kernel, dim3(cdiv(S, 256), cdiv(S, 4), B), dim3(64, 4), 0, (hipStream_t)stream,
+                     (const unsigned char*)imgs, (const S3odPreDesc*)descs, S, vec, out);
+  return s3od_check_launch("preprocess_batch");
+}
+
+// iou_logits: fp32 [B][NM]; ious: fp32 [B][NM] = sigmoid; best: int32 [B] = index of the first maximum of ious
+int s3od_best_index(const float* iou_logits, int B, int NM, float* ious, int* best, void* stream) {
+  S3OD_REQUIRE(B >= 1 && NM >= 1 && NM <= 64, "best_index: bad batch / mask count");
+  hipLaunchKernelGGL(best_index_kernel, dim3(cdiv(B, 64)), dim3(64), 0, (hipStream_t)stream, iou_logits, B, NM, ious, best);
+  return s3od_check_launch("best_index");
+}
+
+// logits: fp32 [B][NM][LH][LW]; best: device int32 [B]; imgs: the packed uint8 source images (nullable when rgba is);
+// descs / descs_host: the same S3odPostDesc[B] table in device and host memory.  all_masks != 0: masks holds
+// [NM][H0][W0] per image at mask_off, otherwise only the best plane [H0][W0].  rgba (nullable): uint8 [H0][W0][4] per
+// image at rgba_off = source RGB + alpha (unsigned char)(best mask * 255).
+int s3od_postprocess_batch(const float* logits, int B, int NM, int LH, int LW, const int* best, const void* imgs,
+                           const void* descs, const void* descs_host, int all_masks, float* masks, void* rgba, float* tmp,
+                           void* stream) {
+  S3OD_REQUIRE(B >= 1 && NM >= 1 && NM <= 64 && (long)B * NM <= 65535 && descs_host != nullptr,
+               "postprocess_batch: bad batch / mask count");
+  S3OD_REQUIRE(best != nullptr && masks != nullptr, "postprocess_batch: best index / mask buffer missing");
+  S3OD_REQUIRE(rgba == nullptr || (imgs != nullptr && (uintptr_t)rgba % 4 == 0), "postprocess_batch: RGBA output needs the source images and 4-byte alignment");
+  const S3odPostDesc* hd = (const S3odPostDesc*)descs_host;
+  int fw = 0, fh = 0, tw = 0, th = 0, tH = 0;                 // tile-kernel and two-pass launch extents
+  for (int b = 0; b < B; b++) {
+    const S3odPostDesc& d = hd[b];
+    S3OD_REQUIRE(d.h > 0 && d.w > 0, "postprocess_batch: image %d: bad crop", b);
+    S3OD_REQUIRE(d.H0 > 0 && d.W0 > 0 && d.H0 <= 65535 && d.h <= 65535, "postprocess_batch: image %d: output size out of range", b);
+    S3OD_REQUIRE(d.pad_h >= 0 && d.pad_w >= 0 && d.pad_h + d.h <= LH && d.pad_w + d.w <= LW,
+                 "postprocess_batch: image %d: crop outside the logits", b);
+    S3OD_REQUIRE(d.mask_off >= 0 && d.rgba_off >= 0 && d.rgba_off % 4 == 0 && d.img_off >= 0 && d.tmp_off >= 0,
+                 "postprocess_batch: image %d: bad offset", b);
+    if (post_fused(d.h, d.w, d.H0, d.W0)) {
+      fw = d.W0 > fw ? d.W0 : fw; fh = d.H0 > fh ? d.H0 : fh;
+    } else {
+      S3OD_REQUIRE(tmp != nullptr, "postprocess_batch: image %d needs the two-pass scratch", b);
+      tw = d.W0 > tw ? d.W0 : tw; th = d.h > th ? d.h : th; tH = d.H0 > tH ? d.H0 : tH;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int planes = all_masks ? NM : 1;
+  const S3odPostDesc* dd = (const S3odPostDesc*)descs;
+  if (fw > 0)
+    hipLaunchKernelGGL(post_tile_kernel, dim3(cdiv(fw, PT_W), cdiv(fh, PT_H), B * planes), dim3(256), 0, st, logits, NM, LH, LW,
+                       best, (const unsigned char*)imgs, dd, planes, masks, (unsigned char*)rgba);
+  if (tw > 0) {
+    hipLaunchKernelGGL(post_h_batch_kernel, dim3(cdiv(tw, 256), th, B * planes), dim3(256), 0, st, logits, NM, LH, LW, best, dd,
+                       planes, tmp);
+    hipLaunchKernelGGL(post_v_batch_kernel, dim3(cdiv(tw, 256), tH, B * planes), dim3(256), 0, st, (const float*)tmp, NM, best,
+                       (const unsigned char*)imgs, dd, planes, masks, (unsigned char*)rgba);
+  }
+  return s3od_check_launch("postprocess_batch");
 }
 
 }  // extern "C"

@@ -143,24 +143,27 @@ def read_gray_u8(path):
     return ((4899 * a[..., 0] + 9617 * a[..., 1] + 1868 * a[..., 2] + 8192) >> 14).astype(np.uint8)
 
 
-def process_dataset(data_dir: str, predictor, compute_best_metrics: bool = False):
+def process_dataset(data_dir: str, predictor, compute_best_metrics: bool = False, batch_size: int = 1):
     """compute_metrics.py:42-100: predict every ``images/*`` file, score it against ``masks/``.
 
     ``predictor.predict(rgb_uint8)`` must return an object with ``soft_mask`` (and, for
     ``compute_best_metrics``, ``has_multiple_masks`` / ``num_masks`` / ``all_masks``), as
     ``SODPredictor`` (``s3od_amd.predictor.SODPredictor``) does.  Image decoding uses PIL (cv2 is
-    not part of this stack); ``> 128`` thresholding of the grey mask as the reference."""
+    not part of this stack); ``> 128`` thresholding of the grey mask as the reference.
+    ``batch_size > 1`` decodes that many images at a time and calls ``predictor.predict_many`` when
+    the predictor has it; the metrics are fed in the same order as with ``batch_size=1``."""
     from PIL import Image
+    if batch_size < 1:
+        raise ValueError(f"batch_size must be >= 1, got {batch_size}")
     images = glob.glob(f"{data_dir}/images/*")
     counter = EvaluationMetrics(device="cuda")
     best = EvaluationMetrics(device="cuda") if compute_best_metrics else None
-    for image_path in images:
-        image = np.asarray(Image.open(image_path).convert("RGB"))
-        result = predictor.predict(image)
+
+    def score(image_path, result):
         gt_path = find_gt_mask_path(image_path, data_dir)
         if not gt_path:
             print(f"Warning: GT mask not found for {image_path}")
-            continue
+            return
         gt_mask = (read_gray_u8(gt_path) > 128).astype(np.float32)
         gt_t = torch.from_numpy(gt_mask).cuda()
         soft = torch.as_tensor(result.soft_mask)
@@ -179,6 +182,17 @@ def process_dataset(data_dir: str, predictor, compute_best_metrics: bool = False
                 if chosen is None:
                     chosen = soft
             best.step(chosen, gt_t.clone())
+
+    if batch_size > 1 and hasattr(predictor, "predict_many"):
+        for i in range(0, len(images), batch_size):
+            paths = images[i:i + batch_size]
+            decoded = [np.asarray(Image.open(p).convert("RGB")) for p in paths]
+            for image_path, result in zip(paths, predictor.predict_many(decoded, batch_size=batch_size)):
+                score(image_path, result)
+    else:
+        for image_path in images:
+            image = np.asarray(Image.open(image_path).convert("RGB"))
+            score(image_path, predictor.predict(image))
     pred_metrics = counter.compute_metrics()
     if compute_best_metrics:
         return {"pred_metrics": pred_metrics, "best_metrics": best.compute_metrics()}

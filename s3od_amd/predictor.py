@@ -6,6 +6,9 @@ emulation) + ImageNet normalisation -> DINOv3/DPT forward -> sigmoid -> unpad ->
 bilinear resize back to the original size, all in libs3od_hip.so; only the 3 IoU scores,
 the masks and the RGBA composition come back to the host, as in the reference.
 
+``remove_background_many(images, threshold, batch_size, return_all_masks)`` does the same for a list
+of differently sized images, ``batch_size`` per forward (``infer_many.py``).
+
 Model loading is offline-safe: a local checkpoint path is tried first (``torch.load`` with
 ``weights_only=True``; ``{"state_dict": ...}``, Lightning ``model.``-prefixed and both
 transformers key layouts are accepted), then the Hugging Face cache (``local_files_only``).
@@ -23,7 +26,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Any, Dict, Optional, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -60,6 +63,7 @@ class BackgroundRemoval:
         self.model.eval()
         self.mean = np.array([0.485, 0.456, 0.406])
         self.std = np.array([0.229, 0.224, 0.225])
+        self._many = None           # staging buffers of remove_background_many, built on first use
 
     @classmethod
     def from_pretrained(cls, model_id: str, **kwargs):
@@ -135,6 +139,46 @@ class BackgroundRemoval:
         rgba = np.dstack([image, alpha])
         return RemovalResult(predicted_mask=predicted_mask, all_masks=all_masks, all_ious=pred_ious,
                              rgba_image=Image.fromarray(rgba, mode="RGBA"))
+
+    @torch.no_grad()
+    def remove_background_many(self, images: Sequence[Union[np.ndarray, Image.Image]], threshold: float = 0.5,
+                               batch_size: int = 8, return_all_masks: bool = True) -> List[RemovalResult]:
+        """``remove_background`` over a list of differently sized images, ``batch_size`` per forward
+        (s3od_preprocess_batch / s3od_postprocess_batch, see ``infer_many.BatchEngine``).  Results come back
+        in input order.  ``return_all_masks=False`` leaves ``all_masks`` None and brings only the best mask
+        and the RGBA image back from the device.  Under ``exact_reference_quirks`` every image is validated
+        before any GPU work (odd padding raises, naming the image's index) and Quirk-2 images, which cannot
+        share the S x S canvas, take the single-image path."""
+        from .infer_many import BatchEngine, classify_geometry
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        arrays = [np.array(im.convert("RGB")) if isinstance(im, Image.Image) else im for im in images]
+        S = self.image_size
+        classes = []
+        for i, a in enumerate(arrays):
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"image {i}: expected an H x W x 3 array, got shape {a.shape}")
+            classes.append(classify_geometry(a.shape[0], a.shape[1], S, self.exact_reference_quirks, index=i))
+        results: List[Optional[RemovalResult]] = [None] * len(arrays)
+        batched = [i for i, c in enumerate(classes) if c == "batched"]
+        geoms = []
+        for i in batched:
+            info = get_pad_info(arrays[i], S)
+            nh, nw = info["resized_size"]
+            geoms.append((nh, nw, info["height_pad"], info["width_pad"], info["height_pad"], info["width_pad"]))
+        if self._many is None:
+            self._many = BatchEngine(self.model, S, self.device)
+        contiguous = [np.ascontiguousarray(arrays[i], dtype=np.uint8) for i in batched]
+        outs = self._many.run(contiguous, geoms, batch_size, self.model.num_outputs, all_masks=return_all_masks)
+        for i, (ious, best, masks, rgba) in zip(batched, outs):     # the image wraps the rgba array it owns: no second copy
+            results[i] = RemovalResult(predicted_mask=masks[best] if return_all_masks else masks[0],
+                                       all_masks=masks if return_all_masks else None, all_ious=ious,
+                                       rgba_image=Image.frombuffer("RGBA", (rgba.shape[1], rgba.shape[0]), rgba, "raw", "RGBA", 0, 1))
+        for i, c in enumerate(classes):
+            if c == "single":
+                r = self.remove_background(arrays[i], threshold)
+                results[i] = r if return_all_masks else RemovalResult(r.predicted_mask, None, r.all_ious, r.rgba_image)
+        return results
 
     @torch.no_grad()
     def remove_background_batch(self, images: torch.Tensor) -> Dict[str, torch.Tensor]:

@@ -23,7 +23,7 @@ plain dict (``hyper_parameters.config.model``); otherwise the variant is inferre
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -67,6 +67,7 @@ class SODPredictor:
         self.model = self._load_checkpoint(checkpoint_path, compute_dtype)
         self.model.to(device)
         self.model.eval()
+        self._many = None           # staging buffers of predict_many, built on first use
 
     def _load_checkpoint(self, checkpoint_path, compute_dtype):
         """predictor.py:358-372: Lightning checkpoint -> model from its config, else a saved model."""
@@ -129,3 +130,32 @@ class SODPredictor:
         soft = all_masks[int(ious.argmax())]
         return PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft,
                                 all_masks=(all_masks > threshold).astype(np.float32), all_ious=ious)
+
+    @torch.no_grad()
+    def predict_many(self, images: Sequence[np.ndarray], threshold: float = 0.5, batch_size: int = 8) -> List[PredictionResult]:
+        """``predict`` over a list of differently sized images, ``batch_size`` per forward, results in input
+        order (s3od_preprocess_batch / s3od_postprocess_batch with this predictor's geometry: the
+        albumentations letterbox for the canvas, ``get_pad_info`` for the crop)."""
+        from .infer_many import BatchEngine
+        if batch_size < 1:
+            raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        arrays = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+        geoms = []
+        for a in arrays:
+            info = self.get_pad_info(a)
+            nh, nw, top, left = self.letterbox(a.shape[0], a.shape[1])
+            geoms.append((nh, nw, top, left, info["height_pad"], info["width_pad"]))
+        if self._many is None:
+            self._many = BatchEngine(self.model, self.image_size, self.device)
+        NM = self.model.num_outputs
+        outs = self._many.run(arrays, geoms, batch_size, NM, all_masks=True, want_rgba=False)
+        results = []
+        for ious, best, masks, _ in outs:
+            if NM == 1:
+                soft = masks[0]
+                results.append(PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft))
+                continue
+            soft = masks[best]
+            results.append(PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft,
+                                            all_masks=(masks > threshold).astype(np.float32), all_ious=ious))
+        return results

@@ -56,6 +56,9 @@ REF = {
     "s3od_eval_metrics": "EvaluationMetrics.step (MAE, MaxF/AvgF, S-measure) + EMeasure + WeightedFMeasure on device: synth_sod/src/synth_sod/model_training/metrics.py:14-424",
     "s3od_eval_metrics_ws": "scratch size of s3od_eval_metrics (new; the reference allocates numpy temporaries)",
     "s3od_preprocess": "BackgroundRemoval._preprocess normalisation: src/s3od/predictor.py:79-94",
+    "s3od_preprocess_batch": "BackgroundRemoval._preprocess over a list of differently sized images, one launch (S3odPreDesc table): src/s3od/predictor.py:79-94",
+    "s3od_best_index": "sigmoid(pred_iou) + argmax per image on device: src/s3od/predictor.py:113-116, 125",
+    "s3od_postprocess_batch": "remove_background post-processing over a batch (S3odPostDesc table): sigmoid, unpad, antialiased resize, best-mask alpha + RGBA: src/s3od/predictor.py:113-132, src/s3od/utils.py:32-37",
     "s3od_linear_wgrad_ws": "workspace query of s3od_linear_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_conv_wgrad_ws": "workspace query of s3od_conv_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_token_prefix_bwd": "cat([cls, register_tokens, patches]) backward: tf:modeling_dinov3_vit.py:88-92 (reference: implicit torch autograd)",
@@ -98,6 +101,19 @@ def collect():
     return out
 
 
+STRUCT = re.compile(r"^struct (S3od\w+) \{[^\n]*\n(?:  [^\n]*\n)+\};", re.M)
+
+
+def structs():
+    """The descriptor structs of the batched entries (struct S3od* in csrc/*.hip), restated as C with /* */ comments."""
+    out = []
+    for f in sorted((ROOT / "s3od_amd" / "csrc").glob("*.hip")):
+        for m in STRUCT.finditer(f.read_text()):
+            body = [re.sub(r"//\s*(.*?)\s*$", r"/* \1 */", ln) for ln in m.group(0).splitlines()]
+            out.append((m.group(1), body, f.name))
+    return out
+
+
 def nrep():
     m = re.search(r"constexpr int S3OD_NREP = (\d+);", (ROOT / "s3od_amd" / "csrc" / "common.hpp").read_text())
     return int(m.group(1))
@@ -130,6 +146,10 @@ def main():
         "#endif",
         "",
     ]
+    for name, body, src in structs():
+        lines.append(f"/* per-image descriptor table entry of the batched image entries (packed array, natural alignment)  [{src}] */")
+        lines += body
+        lines.append("")
     for name, ret, args, src in decls:
         lines.append(f"/* {REF[name]}  [{src}]" + (f"\n * buffers: {WS[name]}" if name in WS else "") + " */")
         lines.append(f"{ret} {name}({args});")
