@@ -94,7 +94,178 @@ struct S3odPostDesc {  // 56 bytes
   int H0;              // @48 output height
   int W0;              // @52 output width
 };
-static_assert(sizeof(S3odPreDesc) == 32 && sizeof(S3odPostDesc) == 56, "descriptor layout is part of the C ABI");
+struct S3odOutDesc {   // 40 bytes
+  long bg_off;         // @0  byte offset of the uint8 [H0][W0][3] background image in the packed image buffer (mode 2 only)
+  long out_off;        // @8  byte offset of this output in the packed output buffer (dense rows; a multiple of 4 for mode 0)
+  long stats_off;      // @16 byte offset of the image's 288-byte counter block in the stats buffer, < 0: none (first row only)
+  long scratch_off;    // @24 offset in floats of the image's [NM][H0][W0] planes in the stats scratch (first row only)
+  int mode;            // @32 0 RGBA, 1 RGB over colour, 2 RGB over image, 3 mask as uint8, 4 nothing
+  int color;           // @36 background colour r | g << 8 | b << 16 (mode 1)
+};
+static_assert(sizeof(S3odPreDesc) == 32 && sizeof(S3odPostDesc) == 56 && sizeof(S3odOutDesc) == 40,
+              "descriptor layout is part of the C ABI");
+
+// ---------------------------------------------------------------- compositing (src/s3od/visualizer.py:17-21)
+enum { OUT_RGBA = 0, OUT_RGB_OVER_COLOR = 1, OUT_RGB_OVER_IMAGE = 2, OUT_MASK_U8 = 3, OUT_NONE = 4 };
+
+static inline __host__ __device__ int out_bpp(int mode) {
+  return mode == OUT_RGBA ? 4 : (mode == OUT_MASK_U8 ? 1 : (mode == OUT_NONE ? 0 : 3));
+}
+
+// One output pixel from the mask value m, the source pixel s and the background pixel (bg, or the packed colour when
+// bg is null).  The blend is numpy's float32 evaluation of (mask * image + (1 - mask) * background).astype(uint8):
+// two separately rounded products, a rounded 1 - m, one rounded add, truncation.  Contraction is off for the blend:
+// hipcc would otherwise fuse a * b + c * d into an FMA, which changes bytes (so does the lerp bg + m (s - bg)).
+// vec4: dst is 4-byte aligned (RGBA only).
+DEV void compose_px(int mode, float m, const unsigned char* __restrict__ s, int color, const unsigned char* __restrict__ bg,
+                    unsigned char* __restrict__ dst, bool vec4) {
+  if (mode == OUT_RGBA) {
+    const unsigned char a = (unsigned char)(m * 255.f);
+    if (vec4) {
+      *(uchar4*)dst = make_uchar4(s[0], s[1], s[2], a);
+    } else {
+      dst[0] = s[0]; dst[1] = s[1]; dst[2] = s[2]; dst[3] = a;
+    }
+  } else if (mode == OUT_MASK_U8) {
+    dst[0] = (unsigned char)(m * 255.f);
+  } else if (mode == OUT_RGB_OVER_COLOR || mode == OUT_RGB_OVER_IMAGE) {
+#pragma clang fp contract(off)
+    const float om = 1.f - m;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const int b = bg != nullptr ? bg[c] : (color >> (8 * c)) & 255;
+      const float fg = m * (float)s[c], rest = om * (float)b;
+      dst[c] = (unsigned char)(fg + rest);
+    }
+  }
+}
+
+// the outputs of pixel (x, y) of image b in the batched kernels: the rows of its descriptor table, or (od null, the
+// entry without a table) the RGBA image at d.rgba_off
+DEV void compose_rows(const S3odOutDesc* __restrict__ od, int n_out, int b, const S3odPostDesc& d, float m, long pix,
+                      const unsigned char* __restrict__ imgs, unsigned char* __restrict__ out) {
+  const unsigned char* s = imgs + d.img_off + pix * 3;
+  if (od == nullptr) {
+    compose_px(OUT_RGBA, m, s, 0, nullptr, out + d.rgba_off + pix * 4, true);
+    return;
+  }
+  for (int k = 0; k < n_out; k++) {
+    const S3odOutDesc* o = od + (long)b * n_out + k;
+    const int mode = o->mode;
+    const unsigned char* bg = mode == OUT_RGB_OVER_IMAGE ? imgs + o->bg_off + pix * 3 : nullptr;
+    compose_px(mode, m, s, o->color, bg, out + o->out_off + pix * out_bpp(mode), true);
+  }
+}
+
+// standalone compositor: one thread per pixel, rows `pitch` bytes apart
+__global__ __launch_bounds__(256) void compose_kernel(const float* __restrict__ mask, const unsigned char* __restrict__ src,
+                                                      int H0, int W0, int mode, int color,
+                                                      const unsigned char* __restrict__ bg, unsigned char* __restrict__ out,
+                                                      long pitch, int vec4) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= W0 || y >= H0) return;
+  const long pix = (long)y * W0 + x;
+  compose_px(mode, mask[pix], src != nullptr ? src + pix * 3 : nullptr, color, bg != nullptr ? bg + pix * 3 : nullptr,
+             out + (long)y * pitch + (long)x * out_bpp(mode), vec4 != 0);
+}
+
+// ---------------------------------------------------------------- mask statistics
+// counter block of one image: 72 uint32 words.  Pair (i, j), i < j < 8, has the fixed slot k = i (15 - i) / 2 + j - i - 1;
+// plane c has the slot 56 + c for its own count #(m_c > 0.5), the diagonal of both pair matrices.
+constexpr int ST_MAXNM = 8, ST_PAIRS = 28;
+constexpr int ST_INTER = 0, ST_UNION = ST_PAIRS, ST_PLANE = 2 * ST_PAIRS, ST_AREA = 64, ST_X0 = 65, ST_Y0 = 66, ST_X1 = 67, ST_Y1 = 68;
+constexpr int ST_WORDS = 72, ST_MAXBLK = 1024;
+
+DEV void stats_init(unsigned* __restrict__ st) {
+  const int t = threadIdx.x;
+  if (t < ST_WORDS) st[t] = (t == ST_X0 || t == ST_Y0) ? 0x7fffffffu : 0u;
+}
+
+DEV int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+DEV int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+
+// Block `blk` of `nblk` (256 threads) counts its share of the N = H0 W0 pixels of planes [NM][N]: one wave-wide ballot
+// per plane (lanes past N do not vote); lane c keeps plane c's ballot, lane k < 28 fetches the two ballots of its pair
+// and adds the popcounts of their AND / OR (lane 28 + c: plane c with itself, its own count); wave partials in LDS, one
+// integer atomic per counter per block.  Integer
+// atomics: the result does not depend on scheduling.  MAXNM (4 or 8) >= NM planes are loaded per pixel, the surplus ones
+// from plane NM - 1 again (in bounds) without a vote.
+template <int MAXNM>
+DEV void stats_block(const float* __restrict__ planes, int NM, long N, int W0, int best, float thr, unsigned* __restrict__ st,
+                     int nblk, int blk) {
+  __shared__ unsigned part[4][ST_WORDS];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  int pa = 0, pc = lane;                             // the pair (pa, pc) of slot k = lane < 28
+#pragma unroll
+  for (int a = 0; a < ST_MAXNM - 1; a++)
+    if (pa == a && pc >= ST_MAXNM - 1 - a) { pc -= ST_MAXNM - 1 - a; pa++; }
+  pc = pa + 1 + pc;
+  if (lane >= ST_PAIRS) pa = pc = lane - ST_PAIRS;   // lanes 28..35: plane with itself; beyond: lanes that hold no ballot
+  unsigned inter = 0, uni = 0, area = 0;
+  int x0 = 0x7fffffff, y0 = 0x7fffffff, x1 = 0, y1 = 0;
+  for (long base = (long)blk * 256; base < N; base += (long)nblk * 256) {
+    const long i = base + tid;
+    const bool in = i < N;
+    const long ii = in ? i : N - 1;
+    float v[MAXNM];
+#pragma unroll
+    for (int c = 0; c < MAXNM; c++) v[c] = planes[(long)min(c, NM - 1) * N + ii];
+    unsigned lo = 0, hi = 0;                         // lane c < 8: the ballot of plane c (0 for c >= NM)
+    bool hit = false;
+#pragma unroll
+    for (int c = 0; c < MAXNM; c++) {
+      const unsigned long long bal = __ballot(in && c < NM && v[c] > 0.5f);
+      if (lane == c) { lo = (unsigned)bal; hi = (unsigned)(bal >> 32); }
+      if (c == best) hit = in && v[c] > thr;
+    }
+    const unsigned alo = __shfl((int)lo, pa), ahi = __shfl((int)hi, pa), clo = __shfl((int)lo, pc), chi = __shfl((int)hi, pc);
+    inter += __popc(alo & clo) + __popc(ahi & chi);
+    uni += __popc(alo | clo) + __popc(ahi | chi);
+    area += __popcll(__ballot(hit));
+    if (hit) {
+      const unsigned u = (unsigned)i;                // N <= 65535^2 < 2^32
+      const int y = (int)(u / (unsigned)W0), x = (int)(u - (unsigned)y * (unsigned)W0);
+      x0 = min(x0, x); y0 = min(y0, y); x1 = max(x1, x + 1); y1 = max(y1, y + 1);
+    }
+  }
+  x0 = wave_min_i(x0); y0 = wave_min_i(y0); x1 = wave_max_i(x1); y1 = wave_max_i(y1);
+  if (lane < ST_PAIRS) {
+    part[wave][ST_INTER + lane] = inter;
+    part[wave][ST_UNION + lane] = uni;
+  } else if (lane < ST_PAIRS + ST_MAXNM) {
+    part[wave][ST_PLANE + lane - ST_PAIRS] = inter;
+  }
+  if (lane == 0) {
+    part[wave][ST_AREA] = area;
+    part[wave][ST_X0] = (unsigned)x0; part[wave][ST_Y0] = (unsigned)y0;
+    part[wave][ST_X1] = (unsigned)x1; part[wave][ST_Y1] = (unsigned)y1;
+  }
+  __syncthreads();
+  if (tid <= ST_AREA) {
+    const unsigned v = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid];
+    if (v) atomicAdd(st + tid, v);
+  } else if (tid == ST_X0 || tid == ST_Y0) {
+    atomicMin(st + tid, min(min(part[0][tid], part[1][tid]), min(part[2][tid], part[3][tid])));
+  } else if (tid == ST_X1 || tid == ST_Y1) {
+    atomicMax(st + tid, max(max(part[0][tid], part[1][tid]), max(part[2][tid], part[3][tid])));
+  }
+}
+
+__global__ void stats_init_kernel(unsigned* __restrict__ st) { stats_init(st); }
+
+__global__ __launch_bounds__(256) void mask_stats_kernel(const float* __restrict__ planes, int NM, long N, int W0, int best,
+                                                         float thr, unsigned* __restrict__ st) {
+  if (NM <= 4) stats_block<4>(planes, NM, N, W0, best, thr, st, gridDim.x, blockIdx.x);
+  else stats_block<8>(planes, NM, N, W0, best, thr, st, gridDim.x, blockIdx.x);
+}
 
 // one launch for B images: each thread writes 4 consecutive canvas pixels of one row for the 3 channels, either the
 // resampled image or the normalised zero pixel of the padding (no separate canvas fill).  block (64, 4).
@@ -201,13 +372,27 @@ constexpr int PT_SW = 2 * PT_W + 8, PT_SH = 2 * PT_H + 8;  // source window: sca
 // plane p of image b -> mask index: every mask, or only the best one
 DEV int post_plane(int p, int planes, int NM, int best) { return planes == NM ? p : best; }
 
+// the float value of pixel pix of mask c: into the packed masks (every plane, or the best one alone as plane 0) and,
+// with mask statistics over planes that are not otherwise kept, into the image's [NM][H0][W0] scratch
+DEV void post_store(float* __restrict__ masks, float* __restrict__ scratch, const S3odOutDesc* __restrict__ od, int n_out, int b,
+                    const S3odPostDesc& d, int all_masks, int c, int bi, float acc, long pix) {
+  const long hw = (long)d.H0 * d.W0;
+  if (masks != nullptr) {
+    if (all_masks) masks[d.mask_off + c * hw + pix] = acc;
+    else if (c == bi) masks[d.mask_off + pix] = acc;
+  }
+  if (scratch != nullptr) scratch[od[(long)b * n_out].scratch_off + c * hw + pix] = acc;
+}
+
 // One 64 x 16 output tile of one mask plane per block (256 threads): the sigmoid of the source window is staged in
 // LDS, resampled horizontally into LDS and vertically from LDS; span and normalised weights are computed once per
 // tile column / row.  The block of the best plane also writes the RGBA tile (source RGB + truncated alpha).
 __global__ __launch_bounds__(256) void post_tile_kernel(const float* __restrict__ logits, int NM, int LH, int LW,
                                                         const int* __restrict__ best, const unsigned char* __restrict__ imgs,
-                                                        const S3odPostDesc* __restrict__ descs, int planes,
-                                                        float* __restrict__ masks, unsigned char* __restrict__ rgba) {
+                                                        const S3odPostDesc* __restrict__ descs, int planes, int all_masks,
+                                                        float* __restrict__ masks, unsigned char* __restrict__ rgba,
+                                                        const S3odOutDesc* __restrict__ od, int n_out,
+                                                        float* __restrict__ scratch) {
   __shared__ float src[PT_SH][PT_SW];
   __shared__ float hbuf[PT_SH][PT_W];
   __shared__ float hw[PT_TAPS][PT_W], vw[PT_TAPS][PT_H];
@@ -272,11 +457,8 @@ __global__ __launch_bounds__(256) void post_tile_kernel(const float* __restrict_
     for (int j = 0; j < PT_TAPS; j++)
       if (j < n) acc += vw[j][r] * hbuf[base + j][tx];
     const long pix = (long)oy * d.W0 + ox;
-    masks[d.mask_off + (long)p * d.H0 * d.W0 + pix] = acc;
-    if (alpha) {
-      const unsigned char* s = imgs + d.img_off + pix * 3;
-      *(uchar4*)(rgba + d.rgba_off + pix * 4) = make_uchar4(s[0], s[1], s[2], (unsigned char)(acc * 255.f));
-    }
+    post_store(masks, scratch, od, n_out, b, d, all_masks, c, bi, acc, pix);
+    if (alpha) compose_rows(od, n_out, b, d, acc, pix, imgs, rgba);
   }
 }
 
@@ -298,7 +480,8 @@ __global__ void post_h_batch_kernel(const float* __restrict__ logits, int NM, in
 
 __global__ void post_v_batch_kernel(const float* __restrict__ tmp, int NM, const int* __restrict__ best,
                                     const unsigned char* __restrict__ imgs, const S3odPostDesc* __restrict__ descs, int planes,
-                                    float* __restrict__ masks, unsigned char* __restrict__ rgba) {
+                                    int all_masks, float* __restrict__ masks, unsigned char* __restrict__ rgba,
+                                    const S3odOutDesc* __restrict__ od, int n_out, float* __restrict__ scratch) {
   const int b = blockIdx.z / planes, p = blockIdx.z % planes;
   const S3odPostDesc d = descs[b];
   if (post_fused(d.h, d.w, d.H0, d.W0)) return;
@@ -310,11 +493,32 @@ __global__ void post_v_batch_kernel(const float* __restrict__ tmp, int NM, const
   float acc = 0.f;
   for (int j = 0; j < sp.xsize; j++) acc += aa_weight(sp, j) * col[(long)j * d.W0];
   const long pix = (long)y * d.W0 + x;
-  masks[d.mask_off + (long)p * d.H0 * d.W0 + pix] = acc;
-  if (rgba != nullptr && post_plane(p, planes, NM, bi) == bi) {
-    const unsigned char* s = imgs + d.img_off + pix * 3;
-    *(uchar4*)(rgba + d.rgba_off + pix * 4) = make_uchar4(s[0], s[1], s[2], (unsigned char)(acc * 255.f));
-  }
+  const int c = post_plane(p, planes, NM, bi);
+  post_store(masks, scratch, od, n_out, b, d, all_masks, c, bi, acc, pix);
+  if (rgba != nullptr && c == bi) compose_rows(od, n_out, b, d, acc, pix, imgs, rgba);
+}
+
+// batched mask statistics: grid (blocks, B); the planes of image b are its packed masks or its scratch
+__global__ void stats_init_batch_kernel(const S3odOutDesc* __restrict__ od, int n_out, unsigned char* __restrict__ stats) {
+  const long off = od[(long)blockIdx.x * n_out].stats_off;
+  if (off >= 0) stats_init((unsigned*)(stats + off));
+}
+
+__global__ __launch_bounds__(256) void mask_stats_batch_kernel(const float* __restrict__ planes, int from_scratch, int NM,
+                                                               const int* __restrict__ best,
+                                                               const S3odPostDesc* __restrict__ descs,
+                                                               const S3odOutDesc* __restrict__ od, int n_out, float thr,
+                                                               unsigned char* __restrict__ stats) {
+  const int b = blockIdx.y;
+  const S3odOutDesc* o = od + (long)b * n_out;
+  if (o->stats_off < 0) return;
+  const S3odPostDesc d = descs[b];
+  const long N = (long)d.H0 * d.W0;
+  if ((long)blockIdx.x * 256 >= N) return;
+  const float* pl = planes + (from_scratch ? o->scratch_off : d.mask_off);
+  unsigned* st = (unsigned*)(stats + o->stats_off);
+  if (NM <= 4) stats_block<4>(pl, NM, N, d.W0, best[b], thr, st, gridDim.x, blockIdx.x);
+  else stats_block<8>(pl, NM, N, d.W0, best[b], thr, st, gridDim.x, blockIdx.x);
 }
 
 // sigmoid of the IoU logits and the index of the first maximum (numpy.argmax), one thread per image
@@ -330,6 +534,74 @@ __global__ void best_index_kernel(const float* __restrict__ iou_logits, int B, i
     if (c == 0 || s > bv) { bv = s; bi = c; }
   }
   best[b] = bi;
+}
+
+// the batched post-processing behind s3od_postprocess_batch (no output table: RGBA at rgba_off) and
+// s3od_postprocess_batch_out
+static int post_batch_impl(const float* logits, int B, int NM, int LH, int LW, const int* best, const void* imgs, const void* descs,
+                           const void* descs_host, const void* odescs, const void* odescs_host, int n_out, int all_masks,
+                           float* masks, void* rgba, float* tmp, float* scratch, void* stats, float threshold, void* stream) {
+  S3OD_REQUIRE(B >= 1 && NM >= 1 && NM <= 64 && (long)B * NM <= 65535 && descs_host != nullptr,
+               "postprocess_batch: bad batch / mask count");
+  S3OD_REQUIRE(best != nullptr, "postprocess_batch: best index / mask buffer missing");
+  S3OD_REQUIRE(rgba == nullptr || (imgs != nullptr && (uintptr_t)rgba % 4 == 0), "postprocess_batch: RGBA output needs the source images and 4-byte alignment");
+  const S3odPostDesc* hd = (const S3odPostDesc*)descs_host;
+  const S3odOutDesc* ho = (const S3odOutDesc*)odescs_host;
+  const bool planes_kept = all_masks && masks != nullptr;      // the statistics read the packed masks
+  if (stats != nullptr) {
+    S3OD_REQUIRE(ho != nullptr && NM <= ST_MAXNM && (uintptr_t)stats % 4 == 0, "postprocess_batch: mask statistics need the output table, at most %d masks and an aligned counter buffer", ST_MAXNM);
+    S3OD_REQUIRE(planes_kept || scratch != nullptr, "postprocess_batch: mask statistics need every plane: all masks or the scratch");
+  }
+  if (ho == nullptr || stats == nullptr || planes_kept) scratch = nullptr;
+  int fw = 0, fh = 0, tw = 0, th = 0, tH = 0;                 // tile-kernel and two-pass launch extents
+  long max_n = 0;
+  for (int b = 0; b < B; b++) {
+    const S3odPostDesc& d = hd[b];
+    S3OD_REQUIRE(d.h > 0 && d.w > 0, "postprocess_batch: image %d: bad crop", b);
+    S3OD_REQUIRE(d.H0 > 0 && d.W0 > 0 && d.H0 <= 65535 && d.h <= 65535, "postprocess_batch: image %d: output size out of range", b);
+    S3OD_REQUIRE(d.pad_h >= 0 && d.pad_w >= 0 && d.pad_h + d.h <= LH && d.pad_w + d.w <= LW,
+                 "postprocess_batch: image %d: crop outside the logits", b);
+    S3OD_REQUIRE(d.mask_off >= 0 && d.rgba_off >= 0 && d.rgba_off % 4 == 0 && d.img_off >= 0 && d.tmp_off >= 0,
+                 "postprocess_batch: image %d: bad offset", b);
+    for (int k = 0; ho != nullptr && k < n_out; k++) {
+      const S3odOutDesc& o = ho[(long)b * n_out + k];
+      S3OD_REQUIRE(o.mode >= OUT_RGBA && o.mode <= OUT_NONE, "postprocess_batch: image %d: unknown output mode %d", b, o.mode);
+      S3OD_REQUIRE(o.mode == OUT_NONE || (rgba != nullptr && o.out_off >= 0 && (o.mode != OUT_RGBA || o.out_off % 4 == 0)),
+                   "postprocess_batch: image %d: output buffer missing / bad output offset", b);
+      S3OD_REQUIRE(o.mode != OUT_RGB_OVER_IMAGE || o.bg_off >= 0, "postprocess_batch: image %d: bad background offset", b);
+    }
+    if (stats != nullptr) {
+      const S3odOutDesc& o = ho[(long)b * n_out];
+      S3OD_REQUIRE(o.stats_off % 4 == 0 && o.scratch_off >= 0 && d.W0 <= 65535, "postprocess_batch: image %d: bad statistics offset / size", b);
+      if (o.stats_off >= 0) max_n = (long)d.H0 * d.W0 > max_n ? (long)d.H0 * d.W0 : max_n;
+    }
+    if (post_fused(d.h, d.w, d.H0, d.W0)) {
+      fw = d.W0 > fw ? d.W0 : fw; fh = d.H0 > fh ? d.H0 : fh;
+    } else {
+      S3OD_REQUIRE(tmp != nullptr, "postprocess_batch: image %d needs the two-pass scratch", b);
+      tw = d.W0 > tw ? d.W0 : tw; th = d.h > th ? d.h : th; tH = d.H0 > tH ? d.H0 : tH;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int planes = (all_masks || stats != nullptr) ? NM : 1;
+  const S3odPostDesc* dd = (const S3odPostDesc*)descs;
+  const S3odOutDesc* od = (const S3odOutDesc*)odescs;
+  if (stats != nullptr)
+    hipLaunchKernelGGL(stats_init_batch_kernel, dim3(B), dim3(128), 0, st, od, n_out, (unsigned char*)stats);
+  if (fw > 0)
+    hipLaunchKernelGGL(post_tile_kernel, dim3(cdiv(fw, PT_W), cdiv(fh, PT_H), B * planes), dim3(256), 0, st, logits, NM, LH, LW,
+                       best, (const unsigned char*)imgs, dd, planes, all_masks, masks, (unsigned char*)rgba, od, n_out, scratch);
+  if (tw > 0) {
+    hipLaunchKernelGGL(post_h_batch_kernel, dim3(cdiv(tw, 256), th, B * planes), dim3(256), 0, st, logits, NM, LH, LW, best, dd,
+                       planes, tmp);
+    hipLaunchKernelGGL(post_v_batch_kernel, dim3(cdiv(tw, 256), tH, B * planes), dim3(256), 0, st, (const float*)tmp, NM, best,
+                       (const unsigned char*)imgs, dd, planes, all_masks, masks, (unsigned char*)rgba, od, n_out, scratch);
+  }
+  if (stats != nullptr && max_n > 0)
+    hipLaunchKernelGGL(mask_stats_batch_kernel, dim3(min(cdiv(max_n, 256), ST_MAXBLK), B), dim3(256), 0, st,
+                       planes_kept ? (const float*)masks : (const float*)scratch, planes_kept ? 0 : 1, NM, best, dd, od, n_out,
+                       threshold, (unsigned char*)stats);
+  return s3od_check_launch("postprocess_batch");
 }
 
 extern "C" {
@@ -388,40 +660,61 @@ int s3od_best_index(const float* iou_logits, int B, int NM, float* ious, int* be
 int s3od_postprocess_batch(const float* logits, int B, int NM, int LH, int LW, const int* best, const void* imgs,
                            const void* descs, const void* descs_host, int all_masks, float* masks, void* rgba, float* tmp,
                            void* stream) {
-  S3OD_REQUIRE(B >= 1 && NM >= 1 && NM <= 64 && (long)B * NM <= 65535 && descs_host != nullptr,
-               "postprocess_batch: bad batch / mask count");
-  S3OD_REQUIRE(best != nullptr && masks != nullptr, "postprocess_batch: best index / mask buffer missing");
-  S3OD_REQUIRE(rgba == nullptr || (imgs != nullptr && (uintptr_t)rgba % 4 == 0), "postprocess_batch: RGBA output needs the source images and 4-byte alignment");
-  const S3odPostDesc* hd = (const S3odPostDesc*)descs_host;
-  int fw = 0, fh = 0, tw = 0, th = 0, tH = 0;                 // tile-kernel and two-pass launch extents
-  for (int b = 0; b < B; b++) {
-    const S3odPostDesc& d = hd[b];
-    S3OD_REQUIRE(d.h > 0 && d.w > 0, "postprocess_batch: image %d: bad crop", b);
-    S3OD_REQUIRE(d.H0 > 0 && d.W0 > 0 && d.H0 <= 65535 && d.h <= 65535, "postprocess_batch: image %d: output size out of range", b);
-    S3OD_REQUIRE(d.pad_h >= 0 && d.pad_w >= 0 && d.pad_h + d.h <= LH && d.pad_w + d.w <= LW,
-                 "postprocess_batch: image %d: crop outside the logits", b);
-    S3OD_REQUIRE(d.mask_off >= 0 && d.rgba_off >= 0 && d.rgba_off % 4 == 0 && d.img_off >= 0 && d.tmp_off >= 0,
-                 "postprocess_batch: image %d: bad offset", b);
-    if (post_fused(d.h, d.w, d.H0, d.W0)) {
-      fw = d.W0 > fw ? d.W0 : fw; fh = d.H0 > fh ? d.H0 : fh;
-    } else {
-      S3OD_REQUIRE(tmp != nullptr, "postprocess_batch: image %d needs the two-pass scratch", b);
-      tw = d.W0 > tw ? d.W0 : tw; th = d.h > th ? d.h : th; tH = d.H0 > tH ? d.H0 : tH;
-    }
-  }
+  S3OD_REQUIRE(masks != nullptr, "postprocess_batch: best index / mask buffer missing");
+  return post_batch_impl(logits, B, NM, LH, LW, best, imgs, descs, descs_host, nullptr, nullptr, 0, all_masks, masks, rgba, tmp,
+                         nullptr, nullptr, 0.5f, stream);
+}
+
+// s3od_postprocess_batch with a table of n_out >= 1 S3odOutDesc rows per image ([B][n_out], device and host copy): the
+// block that holds the best mask's value and the source pixel writes every row's output (RGBA, the mask composited
+// over a colour or over a background image packed beside the sources in imgs, or the mask as uint8) into `out`.
+// masks is nullable: no float plane is stored.  stats (nullable): 288-byte counter blocks at stats_off, initialised
+// here on the stream and filled as by s3od_mask_stats with the image's best index and `threshold`; all NM planes are
+// then resampled (tmp_off must leave room for NM planes), into masks when all_masks != 0 and masks is given, otherwise
+// into scratch at scratch_off.
+int s3od_postprocess_batch_out(const float* logits, int B, int NM, int LH, int LW, const int* best, const void* imgs,
+                               const void* descs, const void* descs_host, const void* odescs, const void* odescs_host, int n_out,
+                               int all_masks, float* masks, void* out, float* tmp, float* scratch, void* stats, float threshold,
+                               void* stream) {
+  S3OD_REQUIRE(odescs != nullptr && odescs_host != nullptr && n_out >= 1 && n_out <= 8,
+               "postprocess_batch_out: output descriptor table missing / bad row count");
+  return post_batch_impl(logits, B, NM, LH, LW, best, imgs, descs, descs_host, odescs, odescs_host, n_out, all_masks, masks, out,
+                         tmp, scratch, stats, threshold, stream);
+}
+
+// mask: device fp32 [H0][W0]; src: device uint8 [H0][W0][3] (nullable for mode 3); mode: 0 RGBA (source RGB + alpha
+// (unsigned char)(mask * 255)), 1 RGB over `color` (r | g << 8 | b << 16), 2 RGB over the device image bg [H0][W0][3],
+// 3 the mask as one uint8 channel; out: uint8, row y at out + y * pitch, pitch >= W0 * bytes per pixel (4, 3, 3, 1);
+// bytes between the rows are left untouched.  Modes 1 and 2 are numpy's float32
+// (mask * image + (1 - mask) * background).astype(uint8), byte for byte, for results in (-1, 256).
+int s3od_compose(const float* mask, const void* src, int H0, int W0, int mode, int color, const void* bg, void* out, long pitch,
+                 void* stream) {
+  S3OD_REQUIRE(mode >= OUT_RGBA && mode <= OUT_MASK_U8, "compose: unknown mode %d", mode);
+  S3OD_REQUIRE(H0 > 0 && W0 > 0 && H0 <= 65535 && W0 <= 65535, "compose: image size out of range");
+  S3OD_REQUIRE(mask != nullptr && out != nullptr && (src != nullptr || mode == OUT_MASK_U8), "compose: mask / source / output missing");
+  S3OD_REQUIRE((mode == OUT_RGB_OVER_IMAGE) == (bg != nullptr), "compose: a background image goes with mode 2 and with no other");
+  S3OD_REQUIRE(pitch >= (long)W0 * out_bpp(mode), "compose: pitch shorter than a row");
+  const int vec4 = (uintptr_t)out % 4 == 0 && pitch % 4 == 0;
+  hipLaunchKernelGGL(compose_kernel, dim3(cdiv(W0, 256), H0), dim3(256), 0, (hipStream_t)stream, mask, (const unsigned char*)src,
+                     H0, W0, mode, color, (const unsigned char*)bg, (unsigned char*)out, pitch, vec4);
+  return s3od_check_launch("compose");
+}
+
+// masks: device fp32 [NM][H0][W0], NM <= 8; stats: caller-owned device block of 72 uint32, initialised here on the
+// stream.  Words: [k] = #(m_i > 0.5 && m_j > 0.5) and [28 + k] = #(m_i > 0.5 || m_j > 0.5) for the pair i < j at
+// k = i (15 - i) / 2 + j - i - 1; [56 + c] = #(m_c > 0.5); [64] = #(m_best > threshold); [65..68] = x0, y0, x1, y1 of
+// those pixels' bounding box (x1, y1 exclusive; undefined when the area is 0).  Exact integers for any H0, W0 <= 65535.
+int s3od_mask_stats(const float* masks, int NM, int H0, int W0, int best, float threshold, void* stats, void* stream) {
+  S3OD_REQUIRE(NM >= 1 && NM <= ST_MAXNM, "mask_stats: mask count %d outside 1..%d", NM, ST_MAXNM);
+  S3OD_REQUIRE(H0 > 0 && W0 > 0 && H0 <= 65535 && W0 <= 65535, "mask_stats: image size out of range");
+  S3OD_REQUIRE(masks != nullptr && stats != nullptr && (uintptr_t)stats % 4 == 0 && best >= 0 && best < NM,
+               "mask_stats: masks / counter block missing or best index out of range");
   hipStream_t st = (hipStream_t)stream;
-  const int planes = all_masks ? NM : 1;
-  const S3odPostDesc* dd = (const S3odPostDesc*)descs;
-  if (fw > 0)
-    hipLaunchKernelGGL(post_tile_kernel, dim3(cdiv(fw, PT_W), cdiv(fh, PT_H), B * planes), dim3(256), 0, st, logits, NM, LH, LW,
-                       best, (const unsigned char*)imgs, dd, planes, masks, (unsigned char*)rgba);
-  if (tw > 0) {
-    hipLaunchKernelGGL(post_h_batch_kernel, dim3(cdiv(tw, 256), th, B * planes), dim3(256), 0, st, logits, NM, LH, LW, best, dd,
-                       planes, tmp);
-    hipLaunchKernelGGL(post_v_batch_kernel, dim3(cdiv(tw, 256), tH, B * planes), dim3(256), 0, st, (const float*)tmp, NM, best,
-                       (const unsigned char*)imgs, dd, planes, masks, (unsigned char*)rgba);
-  }
-  return s3od_check_launch("postprocess_batch");
+  const long N = (long)H0 * W0;
+  hipLaunchKernelGGL(stats_init_kernel, dim3(1), dim3(128), 0, st, (unsigned*)stats);
+  hipLaunchKernelGGL(mask_stats_kernel, dim3(min(cdiv(N, 256), ST_MAXBLK)), dim3(256), 0, st, masks, NM, N, W0, best, threshold,
+                     (unsigned*)stats);
+  return s3od_check_launch("mask_stats");
 }
 
 }  // extern "C"

@@ -9,6 +9,11 @@ the masks and the RGBA composition come back to the host, as in the reference.
 ``remove_background_many(images, threshold, batch_size, return_all_masks)`` does the same for a list
 of differently sized images, ``batch_size`` per forward (``infer_many.py``).
 
+Both take ``background=`` (an (r, g, b) colour or an image of the source's size) and ``stats=True``: the subject
+composited over the background (``RemovalResult.composite``, the reference visualizer's blend) and the pairwise
+mask IoU counts, area and bounding box (``RemovalResult.stats``, a ``MaskStats``) are produced on the device, so
+3 B/px and a 288-byte counter block come back in place of float masks (``compose.py``).
+
 Model loading is offline-safe: a local checkpoint path is tried first (``torch.load`` with
 ``weights_only=True``; ``{"state_dict": ...}``, Lightning ``model.``-prefixed and both
 transformers key layouts are accepted), then the Hugging Face cache (``local_files_only``).
@@ -34,6 +39,7 @@ from PIL import Image
 
 from .utils import get_pad_info, remove_padding  # noqa: F401  (re-exported like the reference)
 from .model import DPTSegmentation
+from .compose import MaskStats
 
 
 @dataclass
@@ -42,6 +48,8 @@ class RemovalResult:
     all_masks: np.ndarray
     all_ious: np.ndarray
     rgba_image: Image.Image
+    composite: Optional[Image.Image] = None     # the subject over ``background`` (RGB), when one was given
+    stats: Optional[MaskStats] = None           # with ``stats=True``
 
 
 class BackgroundRemoval:
@@ -101,6 +109,11 @@ class BackgroundRemoval:
         return info
 
     def _preprocess(self, image: np.ndarray) -> Tuple[torch.Tensor, Dict[str, Any]]:
+        x, info, _ = self._preprocess_dev(image)
+        return x, info
+
+    def _preprocess_dev(self, image: np.ndarray) -> Tuple[torch.Tensor, Dict[str, Any], torch.Tensor]:
+        """-> the model input, the padding info and the uploaded uint8 image."""
         from ._lib import lib, stream
         info = self._pad_info(image)
         S = self.image_size
@@ -111,17 +124,25 @@ class BackgroundRemoval:
         if self.exact_reference_quirks and info["height_pad"] == 0 and info["width_pad"] == 0 and (nh, nw) != (S, S):
             # Quirk 2: `padded = resized` -> the model sees the nh x nw image (it sits at the canvas origin)
             x = x[:, :, :nh, :nw]
-        return x, info
+        return x, info, img
 
     @torch.no_grad()
-    def remove_background(self, image: Union[np.ndarray, Image.Image], threshold: float = 0.5) -> RemovalResult:
+    def remove_background(self, image: Union[np.ndarray, Image.Image], threshold: float = 0.5, *, background=None,
+                          stats: bool = False) -> RemovalResult:
+        """``background``: None, an (r, g, b) tuple or a uint8 array / PIL image of the image's size (any other size
+        raises ``ValueError``; backgrounds are not resized) -> ``result.composite``, the subject over it as a PIL RGB
+        image.  ``stats=True`` -> ``result.stats`` (``MaskStats``); ``threshold`` sets its ``area`` and ``bbox`` and
+        nothing else.  Both run on the device masks (s3od_compose, s3od_mask_stats)."""
         from ._lib import lib, stream
+        from .compose import MAX_STAT_MASKS, compose, mask_stats_words
+        from .infer_many import MODE_RGB_OVER_COLOR, MODE_RGB_OVER_IMAGE, normalize_background
         if isinstance(image, Image.Image):
             image_pil = image.convert("RGB")
             image = np.array(image_pil)
         else:
             image_pil = Image.fromarray(image)
-        x, pad = self._preprocess(image)
+        bg = normalize_background(background, image.shape[:2])
+        x, pad, img_dev = self._preprocess_dev(image)
         out = self.model(x)
         H0, W0 = pad["original_size"]
         LH, LW = out["pred_masks"].shape[2], out["pred_masks"].shape[3]
@@ -137,21 +158,43 @@ class BackgroundRemoval:
         predicted_mask = all_masks[best_idx]
         alpha = (predicted_mask * 255).astype(np.uint8)
         rgba = np.dstack([image, alpha])
+        composite = mask_stats = None
+        if bg is not None:
+            if isinstance(bg, int):
+                comp = compose(masks[best_idx], img_dev, MODE_RGB_OVER_COLOR, bg)
+            else:
+                comp = compose(masks[best_idx], img_dev, MODE_RGB_OVER_IMAGE, 0, torch.from_numpy(bg).to(self.device))
+            composite = Image.fromarray(comp.cpu().numpy())
+        if stats:
+            if NM > MAX_STAT_MASKS:
+                raise ValueError(f"stats=True supports at most {MAX_STAT_MASKS} masks, the model predicts {NM}")
+            words = mask_stats_words(masks, int(best_idx), threshold).cpu().numpy().view(np.uint32)
+            mask_stats = MaskStats.from_words(words, NM)
         return RemovalResult(predicted_mask=predicted_mask, all_masks=all_masks, all_ious=pred_ious,
-                             rgba_image=Image.fromarray(rgba, mode="RGBA"))
+                             rgba_image=Image.fromarray(rgba, mode="RGBA"), composite=composite, stats=mask_stats)
 
     @torch.no_grad()
     def remove_background_many(self, images: Sequence[Union[np.ndarray, Image.Image]], threshold: float = 0.5,
-                               batch_size: int = 8, return_all_masks: bool = True) -> List[RemovalResult]:
+                               batch_size: int = 8, return_all_masks: bool = True, background=None, stats: bool = False,
+                               return_masks: bool = True, return_rgba: bool = True) -> List[RemovalResult]:
         """``remove_background`` over a list of differently sized images, ``batch_size`` per forward
         (s3od_preprocess_batch / s3od_postprocess_batch, see ``infer_many.BatchEngine``).  Results come back
         in input order.  ``return_all_masks=False`` leaves ``all_masks`` None and brings only the best mask
         and the RGBA image back from the device.  Under ``exact_reference_quirks`` every image is validated
         before any GPU work (odd padding raises, naming the image's index) and Quirk-2 images, which cannot
-        share the S x S canvas, take the single-image path."""
-        from .infer_many import BatchEngine, classify_geometry
+        share the S x S canvas, take the single-image path.
+
+        ``background`` (None, one colour or image for every image, or a list with one value per image) and
+        ``stats`` are those of ``remove_background``; the composite is written by the post-processing kernels
+        where they write RGBA, the background images ride in the same staging buffer and upload as the sources,
+        and the counters come from the device masks.  ``return_masks=False`` leaves ``predicted_mask`` and
+        ``all_masks`` None (no float plane leaves the device) and ``return_rgba=False`` leaves ``rgba_image``
+        None; asking for nothing at all raises ``ValueError``."""
+        from .infer_many import BatchEngine, classify_geometry, normalize_backgrounds
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
+        if not (return_masks or return_rgba or stats or background is not None):
+            raise ValueError("nothing requested: return_masks, return_rgba, stats and background are all off")
         arrays = [np.array(im.convert("RGB")) if isinstance(im, Image.Image) else im for im in images]
         S = self.image_size
         classes = []
@@ -159,6 +202,8 @@ class BackgroundRemoval:
             if a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError(f"image {i}: expected an H x W x 3 array, got shape {a.shape}")
             classes.append(classify_geometry(a.shape[0], a.shape[1], S, self.exact_reference_quirks, index=i))
+        bgs = normalize_backgrounds(background, [a.shape[:2] for a in arrays])
+        extras = background is not None or stats or not return_masks or not return_rgba
         results: List[Optional[RemovalResult]] = [None] * len(arrays)
         batched = [i for i, c in enumerate(classes) if c == "batched"]
         geoms = []
@@ -169,15 +214,31 @@ class BackgroundRemoval:
         if self._many is None:
             self._many = BatchEngine(self.model, S, self.device)
         contiguous = [np.ascontiguousarray(arrays[i], dtype=np.uint8) for i in batched]
-        outs = self._many.run(contiguous, geoms, batch_size, self.model.num_outputs, all_masks=return_all_masks)
-        for i, (ious, best, masks, rgba) in zip(batched, outs):     # the image wraps the rgba array it owns: no second copy
-            results[i] = RemovalResult(predicted_mask=masks[best] if return_all_masks else masks[0],
-                                       all_masks=masks if return_all_masks else None, all_ious=ious,
-                                       rgba_image=Image.frombuffer("RGBA", (rgba.shape[1], rgba.shape[0]), rgba, "raw", "RGBA", 0, 1))
+        NM = self.model.num_outputs
+        if not extras:
+            outs = self._many.run(contiguous, geoms, batch_size, NM, all_masks=return_all_masks)
+            outs = [o + (None, None) for o in outs]
+        else:
+            outs = self._many.run(contiguous, geoms, batch_size, NM, all_masks=return_all_masks, want_rgba=return_rgba,
+                                  want_masks=return_masks, backgrounds=[bgs[i] for i in batched], want_stats=stats,
+                                  threshold=threshold)
+        for i, (ious, best, masks, rgba, comp, words) in zip(batched, outs):   # the images wrap the arrays they own: no second copy
+            results[i] = RemovalResult(
+                predicted_mask=None if masks is None else (masks[best] if return_all_masks else masks[0]),
+                all_masks=masks if return_all_masks else None, all_ious=ious,
+                rgba_image=None if rgba is None else
+                Image.frombuffer("RGBA", (rgba.shape[1], rgba.shape[0]), rgba, "raw", "RGBA", 0, 1),
+                composite=comp,
+                stats=None if words is None else MaskStats.from_words(words, NM))
         for i, c in enumerate(classes):
             if c == "single":
-                r = self.remove_background(arrays[i], threshold)
-                results[i] = r if return_all_masks else RemovalResult(r.predicted_mask, None, r.all_ious, r.rgba_image)
+                bg = bgs[i]
+                if isinstance(bg, int):
+                    bg = (bg & 255, bg >> 8 & 255, bg >> 16 & 255)
+                r = self.remove_background(arrays[i], threshold, background=bg, stats=stats)
+                results[i] = RemovalResult(r.predicted_mask if return_masks else None,
+                                           r.all_masks if return_masks and return_all_masks else None, r.all_ious,
+                                           r.rgba_image if return_rgba else None, r.composite, r.stats)
         return results
 
     @torch.no_grad()

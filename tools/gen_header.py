@@ -59,6 +59,9 @@ REF = {
     "s3od_preprocess_batch": "BackgroundRemoval._preprocess over a list of differently sized images, one launch (S3odPreDesc table): src/s3od/predictor.py:79-94",
     "s3od_best_index": "sigmoid(pred_iou) + argmax per image on device: src/s3od/predictor.py:113-116, 125",
     "s3od_postprocess_batch": "remove_background post-processing over a batch (S3odPostDesc table): sigmoid, unpad, antialiased resize, best-mask alpha + RGBA: src/s3od/predictor.py:113-132, src/s3od/utils.py:32-37",
+    "s3od_postprocess_batch_out": "s3od_postprocess_batch with per-image outputs (S3odOutDesc table): RGBA, the visualizer's blend over a colour or an image, the mask as uint8, and the demo's pairwise mask IoU counts: src/s3od/visualizer.py:17-21, demo/app.py:38-56, 98",
+    "s3od_compose": "visualize_removal / visualize_all_masks blend of a finished mask, RGBA and 8-bit mask outputs: src/s3od/visualizer.py:17-21, 45-46, src/s3od/predictor.py:127-130, demo/app.py:98",
+    "s3od_mask_stats": "compute_mask_iou counts for every pair of masks (the demo's ambiguity flag) + area and bounding box of the best mask: demo/app.py:38-56",
     "s3od_linear_wgrad_ws": "workspace query of s3od_linear_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_conv_wgrad_ws": "workspace query of s3od_conv_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_token_prefix_bwd": "cat([cls, register_tokens, patches]) backward: tf:modeling_dinov3_vit.py:88-92 (reference: implicit torch autograd)",
@@ -80,6 +83,8 @@ WS = {
     "s3od_conv_wgrad": "ws (nullable): fp32 [Cout][KH][KW][Cin], all zero on entry, left all zero; slab (nullable): >= s3od_conv_wgrad_ws bytes, contents dead between calls",
     "s3od_avgpool": "ws: fp32 [B][ceil(HW / 1024)][C] partial sums, contents dead between calls (a fixed-order two-pass mean: deterministic)",
     "s3od_colsum": "ws (nullable): >= s3od_colsum_ws bytes of fp32 partial sums, contents dead between calls (with it the sum is two fixed-order passes: deterministic, no same-address atomics; without it one fp32 atomic per column per block)",
+    "s3od_mask_stats": "stats: 72 uint32 words (288 bytes), contents dead on entry: the entry initialises them on the stream. [k] = #(m_i > 0.5 && m_j > 0.5) and [28 + k] = #(m_i > 0.5 || m_j > 0.5) for the pair i < j at k = i (15 - i) / 2 + j - i - 1; [56 + c] = #(m_c > 0.5); [64] = #(m_best > threshold); [65..68] = x0, y0, x1, y1 of those pixels' bounding box (x1, y1 exclusive; without meaning when [64] is 0); [69..71] unused",
+    "s3od_postprocess_batch_out": "stats (nullable): one 288-byte block of 72 uint32 per image at stats_off, initialised on the stream; scratch (nullable): fp32 [NM][H0][W0] per image at scratch_off, needed with stats unless all_masks != 0 and masks is given, contents dead between calls",
     "s3od_linear_wgrad": "slab (nullable): >= s3od_linear_wgrad_ws bytes, contents dead between calls (without it the split-K partials are fp32 atomics into dw)",
 }
 

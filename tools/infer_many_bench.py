@@ -4,6 +4,8 @@ One process, one GPU, 1024 canvas, bf16, synthetic weights.  Both arms run over 
 photo plus deterministic random images of the test shapes scaled x4) and alternate, REPEATS times each:
   (a) loop of remove_background                       -- the baseline, the only way without the batched entry
   (b) remove_background_many at batch_size 4, 8, 16, with return_all_masks True and False
+  (c) remove_background_many at batch_size 8 with background=(255, 255, 255), return_masks=False, return_rgba=False
+      (only the 3 B/px composite comes back), without and with stats=True
 Prints medians and ranges of images/s, the HIP-event time of the batched pre / post kernels against their
 single-image counterparts on the fixture's shape, the host wall time per phase of the batched path (stage =
 fill the pinned buffer and start the upload, launch, wait = block on the download event, split = copy out of the
@@ -101,6 +103,17 @@ def kernel_times(br, image, B=8):
     for name, allm in (("post_batch_all_ms_per_image", 1), ("post_batch_best_ms_per_image", 0)):
         out[name] = event_ms(lambda: L("s3od_postprocess_batch", logits, B, 3, S, S, best, packed, post_d, ctypes.addressof(post),
                                        allm, masks, rgba, tmp, stream())) / B
+    # the composite over white alone (no float plane stored), without and with the mask statistics
+    from s3od_amd.infer_many import MODE_RGB_OVER_COLOR, OutDesc
+    outd = (OutDesc * B)()
+    for b in range(B):
+        outd[b] = OutDesc(0, b * stride, b * 288, b * 3 * H0 * W0, MODE_RGB_OVER_COLOR, 0xFFFFFF)
+    out_d = to_dev(outd)
+    stats = torch.empty(B * 72, dtype=torch.int32, device="cuda")
+    for name, st in (("post_batch_white_ms_per_image", None), ("post_batch_white_stats_ms_per_image", stats)):
+        out[name] = event_ms(lambda: L("s3od_postprocess_batch_out", logits, B, 3, S, S, best, packed, post_d,
+                                       ctypes.addressof(post), out_d, ctypes.addressof(outd), 1, 0, None, rgba, tmp,
+                                       masks if st is not None else None, st, 0.5, stream())) / B
     return out
 
 
@@ -108,7 +121,9 @@ def pcie_bytes(images):
     px = float(np.mean([im.shape[0] * im.shape[1] for im in images]))
     return {"loop": {"h2d": 3 * px, "d2h": 12 * px + 12},
             "many_all_masks": {"h2d": 3 * px + 88, "d2h": 12 * px + 4 * px + 16},
-            "many_best_only": {"h2d": 3 * px + 88, "d2h": 4 * px + 4 * px + 16}}
+            "many_best_only": {"h2d": 3 * px + 88, "d2h": 4 * px + 4 * px + 16},
+            "many_white": {"h2d": 3 * px + 128, "d2h": 3 * px + 16},
+            "many_white_stats": {"h2d": 3 * px + 128, "d2h": 3 * px + 16 + 288}}
 
 
 def main():
@@ -127,6 +142,9 @@ def main():
         for allm in (True, False):
             arms[f"many_bs{bs}_{'all' if allm else 'best'}"] = \
                 (lambda bs=bs, allm=allm: br.remove_background_many(images, batch_size=bs, return_all_masks=allm))
+    white = dict(batch_size=8, background=(255, 255, 255), return_masks=False, return_rgba=False)
+    arms["many_bs8_white"] = lambda: br.remove_background_many(images, **white)
+    arms["many_bs8_white_stats"] = lambda: br.remove_background_many(images, stats=True, **white)
     for fn in arms.values():                       # warm-up: allocator, staging buffers, kernel selection
         fn()
     rates = {k: [] for k in arms}
@@ -135,18 +153,20 @@ def main():
             rates[k].append(n / timed(fn))
     # host wall time per phase of the batched path (one extra pass per mode at batch_size 8, not part of the timings)
     host_ms = {}
-    for allm in (True, False):
-        br.remove_background_many(images[:8], batch_size=8, return_all_masks=allm)
+    modes = {"all": dict(batch_size=8, return_all_masks=True), "best": dict(batch_size=8, return_all_masks=False),
+             "white": white, "white_stats": dict(white, stats=True)}
+    for name, kw in modes.items():
+        br.remove_background_many(images[:8], **kw)
         br._many.host_seconds = {}
-        dt = timed(lambda: br.remove_background_many(images, batch_size=8, return_all_masks=allm))
-        host_ms["all" if allm else "best"] = {**{k: 1e3 * v / n for k, v in br._many.host_seconds.items()}, "total": 1e3 * dt / n}
+        dt = timed(lambda: br.remove_background_many(images, **kw))
+        host_ms[name] = {**{k: 1e3 * v / n for k, v in br._many.host_seconds.items()}, "total": 1e3 * dt / n}
         br._many.host_seconds = None
     rec = {"images": n, "repeats": a.repeats, "canvas": 1024, "dtype": "bf16",
            "images_per_s": {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in rates.items()},
            "host_ms_per_image_bs8": host_ms, "kernels_ms": kernel_times(br, images[0]), "pcie_bytes_per_image": pcie_bytes(images)}
-    print(f"{'arm':<18}{'median':>10}{'min':>10}{'max':>10}   images/s over {n} images, {a.repeats} repeats")
+    print(f"{'arm':<22}{'median':>10}{'min':>10}{'max':>10}   images/s over {n} images, {a.repeats} repeats")
     for k, v in rec["images_per_s"].items():
-        print(f"{k:<18}{v['median']:>10.1f}{v['min']:>10.1f}{v['max']:>10.1f}")
+        print(f"{k:<22}{v['median']:>10.1f}{v['min']:>10.1f}{v['max']:>10.1f}")
     for k, v in host_ms.items():
         print(f"host ms/image at batch_size 8, {k}: " + ", ".join(f"{p} {ms:.2f}" for p, ms in v.items()))
     print(json.dumps(rec))
