@@ -738,12 +738,16 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
     const char* dos = qs_ + I::BYTES;
     const float* lsel = (const float*)(qs_ + 2 * I::BYTES);
     const float* dll = lsel + 64;
-    // accumulators start at -LSE[q] / -delta[q] (q = qb*16 + 4g + i), so after the MFMAs
-    // s = score - lse (log2 units) and dp = dO.v - delta
+    // bf16: accumulators start at -LSE[q] / -delta[q] (q = qb*16 + 4g + i), so after the MFMAs
+    // s = score - lse (log2 units) and dp = dO.v - delta.
+    // f32 (strict parity): they start at zero and -LSE / -delta are added afterwards -- a dot product accumulated
+    // on top of -LSE rounds every partial sum at the magnitude of LSE (16 steps), which cost P two bits (N = 1:
+    // dV = P dO came out 4 ulp off dO); from zero the score is bit-identical to the forward's
     f32x4 s[4][KS], dp[4][KS];
 #pragma unroll
     for (int qb = 0; qb < 4; qb++) {
-      f32x4 nl = *(const f32x4*)(lsel + qb * 16 + 4 * g), nd = *(const f32x4*)(dll + qb * 16 + 4 * g);
+      f32x4 nl = f32x4{0, 0, 0, 0}, nd = f32x4{0, 0, 0, 0};
+      if constexpr (!F32) { nl = *(const f32x4*)(lsel + qb * 16 + 4 * g); nd = *(const f32x4*)(dll + qb * 16 + 4 * g); }
 #pragma unroll
       for (int ks = 0; ks < KS; ks++) { s[qb][ks] = nl; dp[qb][ks] = nd; }
     }
@@ -764,15 +768,18 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
     }
     // P = exp2(S - LSE[q]), dS = P*(dP - delta[q])   (invalid q: LSE = +inf -> P = 0)
 #pragma unroll
-    for (int qb = 0; qb < 4; qb++)
+    for (int qb = 0; qb < 4; qb++) {
+      f32x4 nl = f32x4{0, 0, 0, 0}, nd = f32x4{0, 0, 0, 0};
+      if constexpr (F32) { nl = *(const f32x4*)(lsel + qb * 16 + 4 * g); nd = *(const f32x4*)(dll + qb * 16 + 4 * g); }
 #pragma unroll
       for (int ks = 0; ks < KS; ks++)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-          float p = fexp2(s[qb][ks][i]);
+          float p = fexp2(s[qb][ks][i] + nl[i]);
           s[qb][ks][i] = p;
-          dp[qb][ks][i] = p * dp[qb][ks][i];
+          dp[qb][ks][i] = p * (dp[qb][ks][i] + nd[i]);
         }
+    }
     // dV^T += dO^T P ; dK^T += Q^T dS
     if constexpr (F32) {
 #pragma unroll
@@ -905,7 +912,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 #pragma unroll
     for (int kb = 0; kb < 4; kb++) {
 #pragma unroll
-      for (int qs = 0; qs < QS; qs++) { s[kb][qs] = nl[qs]; dp[kb][qs] = nd[qs]; }
+      for (int qs = 0; qs < QS; qs++) {      // f32: from zero, -LSE / -delta added after the MFMAs (see the dK/dV pass)
+        s[kb][qs] = F32 ? f32x4{0, 0, 0, 0} : nl[qs];
+        dp[kb][qs] = F32 ? f32x4{0, 0, 0, 0} : nd[qs];
+      }
 #pragma unroll
       for (int kk = 0; kk < KK; kk++) {
         if constexpr (F32) {
@@ -925,7 +935,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 #pragma unroll
       for (int qs = 0; qs < QS; qs++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) dp[kb][qs][i] *= fexp2(s[kb][qs][i]);
+        for (int i = 0; i < 4; i++) {
+          if constexpr (F32) dp[kb][qs][i] = (dp[kb][qs][i] + nd[qs][i]) * fexp2(s[kb][qs][i] + nl[qs][i]);
+          else dp[kb][qs][i] *= fexp2(s[kb][qs][i]);
+        }
     if (kt * 64 + 64 > N) {   // last tile: zero dS of keys >= N (exp2(-lse) may overflow)
 #pragma unroll
       for (int kb = 0; kb < 4; kb++)
