@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from .infer_many import MODE_MASK_U8, MODE_RGB_OVER_IMAGE, MODE_RGBA, STATS_WORDS
+from .image_ops import MODE_MASK_U8, MODE_RGB_OVER_IMAGE, MODE_RGBA, STATS_WORDS
 
 MAX_STAT_MASKS = 8
 _BPP = (4, 3, 3, 1)

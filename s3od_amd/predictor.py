@@ -7,7 +7,10 @@ bilinear resize back to the original size, all in libs3od_hip.so; only the 3 IoU
 the masks and the RGBA composition come back to the host, as in the reference.
 
 ``remove_background_many(images, threshold, batch_size, return_all_masks)`` does the same for a list
-of differently sized images, ``batch_size`` per forward (``infer_many.py``).
+of differently sized images, ``batch_size`` per forward (``infer_many.py``).  Both take an image's geometry from
+``_geometry`` (``image_ops.reference_geometry``, the one place that raises Quirk 1 and detects Quirk 2); the
+single-image pipeline is ``image_ops.run_single``, which ``SODPredictor.predict`` shares, and Quirk-2 images of a
+list go through it (``_remove_background``) because they cannot share the S x S canvas.
 
 Both take ``background=`` (an (r, g, b) colour or an image of the source's size) and ``stats=True``: the subject
 composited over the background (``RemovalResult.composite``, the reference visualizer's blend) and the pairwise
@@ -39,7 +42,10 @@ from PIL import Image
 
 from .utils import get_pad_info, remove_padding  # noqa: F401  (re-exported like the reference)
 from .model import DPTSegmentation
-from .compose import MaskStats
+from .compose import MAX_STAT_MASKS, MaskStats, compose, mask_stats_words
+from .image_ops import (MODE_RGB_OVER_COLOR, MODE_RGB_OVER_IMAGE, normalize_background, normalize_backgrounds,
+                        preprocess_single, reference_geometry, run_single)
+from .infer_many import BatchEngine, Request
 
 
 @dataclass
@@ -98,33 +104,14 @@ class BackgroundRemoval:
         return model
 
     # ------------------------------------------------------------------ pre / post
-    def _pad_info(self, image: np.ndarray) -> Dict[str, Any]:
-        info = get_pad_info(image, self.image_size)
-        nh, nw = info["resized_size"]
-        S = self.image_size
-        if self.exact_reference_quirks and ((info["height_pad"] > 0 and S - nh != 2 * info["height_pad"]) or
-                                            (info["width_pad"] > 0 and S - nw != 2 * info["width_pad"])):
-            raise ValueError(f"could not broadcast input array from shape ({nh},{nw},3) into the padded canvas "
-                             f"(reference predictor.py:83-89 behaviour for odd padding)")
-        return info
+    def _geometry(self, h: int, w: int, index: Optional[int] = None) -> Tuple[tuple, bool]:
+        """-> the geometry of an h x w image and whether Quirk 2 applies; odd padding raises (Quirk 1)."""
+        return reference_geometry(h, w, self.image_size, self.exact_reference_quirks, index)
 
     def _preprocess(self, image: np.ndarray) -> Tuple[torch.Tensor, Dict[str, Any]]:
-        x, info, _ = self._preprocess_dev(image)
-        return x, info
-
-    def _preprocess_dev(self, image: np.ndarray) -> Tuple[torch.Tensor, Dict[str, Any], torch.Tensor]:
-        """-> the model input, the padding info and the uploaded uint8 image."""
-        from ._lib import lib, stream
-        info = self._pad_info(image)
-        S = self.image_size
-        nh, nw = info["resized_size"]
-        img = torch.from_numpy(np.ascontiguousarray(image, dtype=np.uint8)).to(self.device)
-        x = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
-        lib()("s3od_preprocess", img, image.shape[0], image.shape[1], nh, nw, info["height_pad"], info["width_pad"], S, x, stream())
-        if self.exact_reference_quirks and info["height_pad"] == 0 and info["width_pad"] == 0 and (nh, nw) != (S, S):
-            # Quirk 2: `padded = resized` -> the model sees the nh x nw image (it sits at the canvas origin)
-            x = x[:, :, :nh, :nw]
-        return x, info, img
+        geom, quirk2 = self._geometry(*image.shape[:2])
+        x, _ = preprocess_single(image, geom, self.image_size, self.device, unpadded=quirk2)
+        return x, get_pad_info(image, self.image_size)
 
     @torch.no_grad()
     def remove_background(self, image: Union[np.ndarray, Image.Image], threshold: float = 0.5, *, background=None,
@@ -133,26 +120,17 @@ class BackgroundRemoval:
         raises ``ValueError``; backgrounds are not resized) -> ``result.composite``, the subject over it as a PIL RGB
         image.  ``stats=True`` -> ``result.stats`` (``MaskStats``); ``threshold`` sets its ``area`` and ``bbox`` and
         nothing else.  Both run on the device masks (s3od_compose, s3od_mask_stats)."""
-        from ._lib import lib, stream
-        from .compose import MAX_STAT_MASKS, compose, mask_stats_words
-        from .infer_many import MODE_RGB_OVER_COLOR, MODE_RGB_OVER_IMAGE, normalize_background
         if isinstance(image, Image.Image):
-            image_pil = image.convert("RGB")
-            image = np.array(image_pil)
-        else:
-            image_pil = Image.fromarray(image)
-        bg = normalize_background(background, image.shape[:2])
-        x, pad, img_dev = self._preprocess_dev(image)
-        out = self.model(x)
-        H0, W0 = pad["original_size"]
-        LH, LW = out["pred_masks"].shape[2], out["pred_masks"].shape[3]
-        h, w = LH - 2 * pad["height_pad"], LW - 2 * pad["width_pad"]
-        NM = out["pred_masks"].shape[1]
-        tmp = torch.empty((NM, h, W0), dtype=torch.float32, device=x.device)
-        masks = torch.empty((NM, H0, W0), dtype=torch.float32, device=x.device)
-        lib()("s3od_sigmoid_unpad_resize", out["pred_masks"].contiguous(), NM, LH, LW, pad["height_pad"], pad["width_pad"], h, w,
-              H0, W0, tmp, masks, stream())
-        pred_ious = torch.sigmoid(out["pred_iou"]).squeeze(0).cpu().numpy()   # 3 floats
+            image = np.array(image.convert("RGB"))
+        return self._remove_background(image, threshold, normalize_background(background, image.shape[:2]), stats)
+
+    def _remove_background(self, image: np.ndarray, threshold: float, bg, stats: bool) -> RemovalResult:
+        """``remove_background`` of an array with the background already normalised (``normalize_background``)."""
+        if image.dtype != np.uint8:
+            raise TypeError(f"an image array is uint8, got {image.dtype}")
+        geom, quirk2 = self._geometry(*image.shape[:2])
+        masks, iou_logits, img_dev = run_single(self.model, image, geom, self.image_size, self.device, unpadded=quirk2)
+        pred_ious = torch.sigmoid(iou_logits).cpu().numpy()   # 3 floats
         all_masks = masks.cpu().numpy()
         best_idx = pred_ious.argmax()
         predicted_mask = all_masks[best_idx]
@@ -166,10 +144,10 @@ class BackgroundRemoval:
                 comp = compose(masks[best_idx], img_dev, MODE_RGB_OVER_IMAGE, 0, torch.from_numpy(bg).to(self.device))
             composite = Image.fromarray(comp.cpu().numpy())
         if stats:
-            if NM > MAX_STAT_MASKS:
-                raise ValueError(f"stats=True supports at most {MAX_STAT_MASKS} masks, the model predicts {NM}")
+            if len(masks) > MAX_STAT_MASKS:
+                raise ValueError(f"stats=True supports at most {MAX_STAT_MASKS} masks, the model predicts {len(masks)}")
             words = mask_stats_words(masks, int(best_idx), threshold).cpu().numpy().view(np.uint32)
-            mask_stats = MaskStats.from_words(words, NM)
+            mask_stats = MaskStats.from_words(words, len(masks))
         return RemovalResult(predicted_mask=predicted_mask, all_masks=all_masks, all_ious=pred_ious,
                              rgba_image=Image.fromarray(rgba, mode="RGBA"), composite=composite, stats=mask_stats)
 
@@ -178,7 +156,7 @@ class BackgroundRemoval:
                                batch_size: int = 8, return_all_masks: bool = True, background=None, stats: bool = False,
                                return_masks: bool = True, return_rgba: bool = True) -> List[RemovalResult]:
         """``remove_background`` over a list of differently sized images, ``batch_size`` per forward
-        (s3od_preprocess_batch / s3od_postprocess_batch, see ``infer_many.BatchEngine``).  Results come back
+        (s3od_preprocess_batch / s3od_postprocess_batch_out, see ``infer_many.BatchEngine``).  Results come back
         in input order.  ``return_all_masks=False`` leaves ``all_masks`` None and brings only the best mask
         and the RGBA image back from the device.  Under ``exact_reference_quirks`` every image is validated
         before any GPU work (odd padding raises, naming the image's index) and Quirk-2 images, which cannot
@@ -190,55 +168,43 @@ class BackgroundRemoval:
         and the counters come from the device masks.  ``return_masks=False`` leaves ``predicted_mask`` and
         ``all_masks`` None (no float plane leaves the device) and ``return_rgba=False`` leaves ``rgba_image``
         None; asking for nothing at all raises ``ValueError``."""
-        from .infer_many import BatchEngine, classify_geometry, normalize_backgrounds
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         if not (return_masks or return_rgba or stats or background is not None):
             raise ValueError("nothing requested: return_masks, return_rgba, stats and background are all off")
         arrays = [np.array(im.convert("RGB")) if isinstance(im, Image.Image) else im for im in images]
-        S = self.image_size
-        classes = []
+        geoms = []
         for i, a in enumerate(arrays):
             if a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError(f"image {i}: expected an H x W x 3 array, got shape {a.shape}")
-            classes.append(classify_geometry(a.shape[0], a.shape[1], S, self.exact_reference_quirks, index=i))
+            geoms.append(self._geometry(a.shape[0], a.shape[1], index=i))
         bgs = normalize_backgrounds(background, [a.shape[:2] for a in arrays])
-        extras = background is not None or stats or not return_masks or not return_rgba
         results: List[Optional[RemovalResult]] = [None] * len(arrays)
-        batched = [i for i, c in enumerate(classes) if c == "batched"]
-        geoms = []
-        for i in batched:
-            info = get_pad_info(arrays[i], S)
-            nh, nw = info["resized_size"]
-            geoms.append((nh, nw, info["height_pad"], info["width_pad"], info["height_pad"], info["width_pad"]))
+        batched = [i for i, (_, quirk2) in enumerate(geoms) if not quirk2]
         if self._many is None:
-            self._many = BatchEngine(self.model, S, self.device)
-        contiguous = [np.ascontiguousarray(arrays[i], dtype=np.uint8) for i in batched]
+            self._many = BatchEngine(self.model, self.image_size, self.device)
         NM = self.model.num_outputs
-        if not extras:
-            outs = self._many.run(contiguous, geoms, batch_size, NM, all_masks=return_all_masks)
-            outs = [o + (None, None) for o in outs]
-        else:
-            outs = self._many.run(contiguous, geoms, batch_size, NM, all_masks=return_all_masks, want_rgba=return_rgba,
-                                  want_masks=return_masks, backgrounds=[bgs[i] for i in batched], want_stats=stats,
-                                  threshold=threshold)
-        for i, (ious, best, masks, rgba, comp, words) in zip(batched, outs):   # the images wrap the arrays they own: no second copy
+        outs = self._many.run([np.ascontiguousarray(arrays[i], dtype=np.uint8) for i in batched],
+                              [geoms[i][0] for i in batched], batch_size, NM,
+                              Request(all_masks=return_all_masks, want_masks=return_masks, want_rgba=return_rgba,
+                                      backgrounds=[bgs[i] for i in batched], want_stats=stats, threshold=threshold))
+        for i, o in zip(batched, outs):     # the images wrap the arrays they own: no second copy
             results[i] = RemovalResult(
-                predicted_mask=None if masks is None else (masks[best] if return_all_masks else masks[0]),
-                all_masks=masks if return_all_masks else None, all_ious=ious,
-                rgba_image=None if rgba is None else
-                Image.frombuffer("RGBA", (rgba.shape[1], rgba.shape[0]), rgba, "raw", "RGBA", 0, 1),
-                composite=comp,
-                stats=None if words is None else MaskStats.from_words(words, NM))
-        for i, c in enumerate(classes):
-            if c == "single":
-                bg = bgs[i]
-                if isinstance(bg, int):
-                    bg = (bg & 255, bg >> 8 & 255, bg >> 16 & 255)
-                r = self.remove_background(arrays[i], threshold, background=bg, stats=stats)
-                results[i] = RemovalResult(r.predicted_mask if return_masks else None,
-                                           r.all_masks if return_masks and return_all_masks else None, r.all_ious,
-                                           r.rgba_image if return_rgba else None, r.composite, r.stats)
+                predicted_mask=None if o.masks is None else o.masks[o.best if return_all_masks else 0],
+                all_masks=o.masks if return_all_masks else None, all_ious=o.ious,
+                rgba_image=None if o.rgba is None else
+                Image.frombuffer("RGBA", (o.rgba.shape[1], o.rgba.shape[0]), o.rgba, "raw", "RGBA", 0, 1),
+                composite=o.composite,
+                stats=None if o.stats_words is None else MaskStats.from_words(o.stats_words, NM))
+        for i, (_, quirk2) in enumerate(geoms):
+            if quirk2:                      # the single-image path, trimmed to what was asked for
+                r = results[i] = self._remove_background(arrays[i], threshold, bgs[i], stats)
+                if not return_rgba:
+                    r.rgba_image = None
+                if not (return_masks and return_all_masks):
+                    r.all_masks = None
+                if not return_masks:
+                    r.predicted_mask = None
         return results
 
     @torch.no_grad()

@@ -4,8 +4,9 @@ model the evaluation loop (``compute_metrics.py:42-100``, ``train.py:30-55``) sc
 
 Device path: uint8 upload -> ``s3od_preprocess`` (LongestMaxSize + centred PadIfNeeded(fill 0) +
 Normalize) -> DPTSegmentation forward -> ``s3od_sigmoid_unpad_resize`` over all N masks (sigmoid,
-``remove_padding`` crop, antialiased bilinear resize to the original size).  Only the final masks
-and the N IoU scores come back to the host, as in the reference.
+``remove_padding`` crop, antialiased bilinear resize to the original size): ``image_ops.run_single``
+with this predictor's ``_geometry``.  Only the final masks and the N IoU scores come back to the host,
+as in the reference.  ``predict_many`` feeds the same geometry to ``infer_many.BatchEngine``.
 
 Kept reference behaviour:
   * ``get_pad_info`` (:374-398) truncates ``int(new_w / aspect_ratio)`` and ``remove_padding``
@@ -29,6 +30,8 @@ import numpy as np
 import torch
 
 from .checkpoint import model_state_dict, read_checkpoint
+from .image_ops import run_single
+from .infer_many import BatchEngine, Request
 from .lightning_module import _get, instantiate
 from .model import DPTSegmentation
 
@@ -47,6 +50,15 @@ class PredictionResult:
     @property
     def num_masks(self) -> int:
         return len(self.all_masks) if self.has_multiple_masks else 1
+
+
+def _result(masks: np.ndarray, ious: Optional[np.ndarray], best: int, threshold: float) -> PredictionResult:
+    """Soft masks [N, H0, W0] -> the result; a single-mask model has no ``all_masks`` / ``all_ious``."""
+    soft = masks[best]
+    binary = (soft > threshold).astype(np.float32)
+    if len(masks) == 1:
+        return PredictionResult(binary_mask=binary, soft_mask=soft)
+    return PredictionResult(binary_mask=binary, soft_mask=soft, all_masks=(masks > threshold).astype(np.float32), all_ious=ious)
 
 
 def _model_from_weights(sd, compute_dtype):
@@ -103,59 +115,26 @@ class SODPredictor:
         nh, nw = (round(h * scale), round(w * scale)) if scale != 1.0 else (h, w)
         return nh, nw, max(0, (S - nh) // 2), max(0, (S - nw) // 2)
 
+    def _geometry(self, h: int, w: int) -> tuple:
+        """The albumentations letterbox for the canvas, ``get_pad_info`` for the crop (``image_ops`` geometry)."""
+        info = self.get_pad_info(np.broadcast_to(np.uint8(0), (h, w)))
+        return (*self.letterbox(h, w), info["height_pad"], info["width_pad"])
+
     @torch.no_grad()
     def predict(self, image: np.ndarray, threshold: float = 0.5) -> PredictionResult:
-        from ._lib import lib, stream
-        image = np.require(image, np.uint8, ["C", "W"])
-        pad_info = self.get_pad_info(image)
-        S = self.image_size
-        H0, W0 = image.shape[:2]
-        nh, nw, top, left = self.letterbox(H0, W0)
-        img = torch.from_numpy(image).to(self.device)
-        x = torch.empty((1, 3, S, S), dtype=torch.float32, device=self.device)
-        lib()("s3od_preprocess", img, H0, W0, nh, nw, top, left, S, x, stream())
-        out = self.model(x)
-        logits = out["pred_masks"][0].contiguous()                 # [N, LH, LW]
-        NM, LH, LW = logits.shape
-        ph, pw = pad_info["height_pad"], pad_info["width_pad"]
-        h, w = LH - 2 * ph, LW - 2 * pw                             # masks[:, ph:-ph, pw:-pw]
-        tmp = torch.empty((NM, h, W0), dtype=torch.float32, device=self.device)
-        masks = torch.empty((NM, H0, W0), dtype=torch.float32, device=self.device)
-        lib()("s3od_sigmoid_unpad_resize", logits, NM, LH, LW, ph, pw, h, w, H0, W0, tmp, masks, stream())
-        all_masks = masks.cpu().numpy()
-        if NM == 1:
-            soft = all_masks[0]
-            return PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft)
-        ious = torch.sigmoid(out["pred_iou"][0]).cpu().numpy()
-        soft = all_masks[int(ious.argmax())]
-        return PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft,
-                                all_masks=(all_masks > threshold).astype(np.float32), all_ious=ious)
+        masks, iou_logits, _ = run_single(self.model, image, self._geometry(*image.shape[:2]), self.image_size, self.device)
+        ious = torch.sigmoid(iou_logits).cpu().numpy() if len(masks) > 1 else None
+        return _result(masks.cpu().numpy(), ious, 0 if ious is None else int(ious.argmax()), threshold)
 
     @torch.no_grad()
     def predict_many(self, images: Sequence[np.ndarray], threshold: float = 0.5, batch_size: int = 8) -> List[PredictionResult]:
         """``predict`` over a list of differently sized images, ``batch_size`` per forward, results in input
-        order (s3od_preprocess_batch / s3od_postprocess_batch with this predictor's geometry: the
-        albumentations letterbox for the canvas, ``get_pad_info`` for the crop)."""
-        from .infer_many import BatchEngine
+        order (``infer_many.BatchEngine`` with this predictor's ``_geometry``)."""
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         arrays = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-        geoms = []
-        for a in arrays:
-            info = self.get_pad_info(a)
-            nh, nw, top, left = self.letterbox(a.shape[0], a.shape[1])
-            geoms.append((nh, nw, top, left, info["height_pad"], info["width_pad"]))
         if self._many is None:
             self._many = BatchEngine(self.model, self.image_size, self.device)
-        NM = self.model.num_outputs
-        outs = self._many.run(arrays, geoms, batch_size, NM, all_masks=True, want_rgba=False)
-        results = []
-        for ious, best, masks, _ in outs:
-            if NM == 1:
-                soft = masks[0]
-                results.append(PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft))
-                continue
-            soft = masks[best]
-            results.append(PredictionResult(binary_mask=(soft > threshold).astype(np.float32), soft_mask=soft,
-                                            all_masks=(masks > threshold).astype(np.float32), all_ious=ious))
-        return results
+        outs = self._many.run(arrays, [self._geometry(*a.shape[:2]) for a in arrays], batch_size, self.model.num_outputs,
+                              Request(want_rgba=False))
+        return [_result(o.masks, o.ious, o.best, threshold) for o in outs]

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 from PIL import Image
 
-from .infer_many import MODE_RGB_OVER_COLOR, pack_color
+from .image_ops import MODE_RGB_OVER_COLOR, pack_color
 
 
 def _upload(image, masks):

@@ -173,6 +173,14 @@ def test_nothing_requested_raises_before_any_gpu_work():
         br.remove_background_many([np.zeros((4, 4, 3), np.uint8)], return_masks=False, return_rgba=False)
 
 
+def test_non_uint8_image_raises_before_any_gpu_work():
+    from s3od import BackgroundRemoval
+    br = BackgroundRemoval.__new__(BackgroundRemoval)         # no model, no device: the check comes first
+    for dtype in (np.float32, np.float64, np.int32):
+        with pytest.raises(TypeError, match="uint8"):
+            br.remove_background(np.zeros((4, 4, 3), dtype))
+
+
 # ---------------------------------------------------------------------------------- kernel resources
 def test_new_kernels_have_no_private_segment_and_no_spills(tmp_path):
     from test_kernel_resources_cpu import LLVM, TOOLS

@@ -339,6 +339,29 @@ def test_many_results_own_their_memory(br):
         assert np.array_equal(r.all_ious, io) and np.array_equal(np.array(r.rgba_image), rgba)
 
 
+def test_many_plain_call_equals_old_entry(br):
+    """The plain call goes through s3od_postprocess_batch_out with one RGBA row per image; it gives, bit for bit, what
+    the same chunks give when driven by hand through s3od_preprocess_batch -> model -> s3od_best_index ->
+    s3od_postprocess_batch (the eval forward has no atomics and the two C entries share one implementation)."""
+    shapes = [(100, 200), (20, 30), (640, 480), (31, 31)]
+    assert {bool(is_two_pass(*post_geometry(s, S)[2:], *s)) for s in shapes} == {True, False}
+    images = rand_images(shapes, 17)
+    many = br.remove_background_many(images, batch_size=2)
+    assert len(many) == len(images)
+    for c in range(0, len(images), 2):
+        chunk = images[c:c + 2]
+        with torch.no_grad():
+            out = br.model(preprocess_batch(chunk, S))
+        old, ious, best = postprocess_batch(out["pred_masks"].float().contiguous(),
+                                            out["pred_iou"].float().reshape(len(chunk), 3).contiguous(), chunk, S)
+        for b, (masks, rgba) in enumerate(old):
+            r = many[c + b]
+            assert np.array_equal(r.all_ious, ious[b]) and int(r.all_ious.argmax()) == best[b], shapes[c + b]
+            assert np.array_equal(r.all_masks, masks), shapes[c + b]
+            assert np.array_equal(r.predicted_mask, masks[best[b]]), shapes[c + b]
+            assert np.array_equal(np.array(r.rgba_image), rgba), shapes[c + b]
+
+
 # ---------------------------------------------------------------------------------- 7. predict_many
 def check_predictions(pred, images, many, threshold=0.5):
     worst = 0.0
