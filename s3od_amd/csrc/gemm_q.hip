@@ -153,7 +153,7 @@ int launch_igemm_q(LA la, LB lb, EPI epi, int M, int N, int KTILES, int split, i
   return s3od_check_launch("igemm_q");
 }
 
-// the (loader, epilogue) combinations the linears use (gemm_ops.hip: s3od_linear_fwd / _dgrad / _wgrad)
+// the (loader, epilogue) combinations the linears use (linear_ops.hip: s3od_linear_fwd / _dgrad / _wgrad)
 typedef DenseKC<bf16, 256, 4> QKC;
 typedef DenseMC<bf16, 256, 4> QMC;
 template int launch_igemm_q<QKC, QKC, EpiStd<bf16, bf16, bf16>>(QKC, QKC, EpiStd<bf16, bf16, bf16>, int, int, int, int, int, hipStream_t);

@@ -33,6 +33,14 @@ def test_library_exports_every_declared_symbol():
         assert len(L.fns[name][0].argtypes) == len(types)
 
 
+def test_removed_variant_knobs_are_not_in_the_library():
+    """The probe and the rejected kernel variants are gone from the product library, not merely unselected."""
+    from s3od_amd._lib import LIB_PATH
+    blob = Path(LIB_PATH).read_bytes()
+    for name in (b"S3OD_EPI_PROBE", b"S3OD_RW_HGB", b"S3OD_WGD_PROD", b"S3OD_WGD_NPROD"):
+        assert name not in blob, name.decode()
+
+
 def test_invalid_argument_reports_error():
     from s3od_amd._lib import lib, HipLibError
     # K not a multiple of 8 is rejected on the host before any launch

@@ -1,5 +1,5 @@
 """GPU: the 3x3 stride-1 convs on the 256x256 ping-pong kernel (csrc/gemm.hpp igemm_pp_kernel with the Conv3A
-loader, selected by conv_pp_ok in csrc/gemm_ops.hip) -- the DPT ResidualConvUnit / layerK_rn convs
+loader, selected by conv_pp_ok in csrc/conv_ops.hip) -- the DPT ResidualConvUnit / layerK_rn convs
 (src/s3od/model.py:223-226,334-345) and their data gradients run as forward convs of dy -- against fp32 PyTorch
 convolutions of the same bf16 operands.  Shapes are chosen so the ping-pong path is the one selected (>= 256 pixel
 tiles filling whole rounds, K >= 9 * 512 or >= 8 rounds), with ragged image sizes (partial rows, an M tail past the

@@ -1,7 +1,8 @@
 """Register / scratch audit of the built gfx950 code objects (CPU; reads build/*.o, no GPU).
 
 The kernels that pace their vector-memory queue with hand-counted `s_waitcnt vmcnt(N)` (the LDS-DMA rings of the GEMM
-engine, the register-weight convs and the DMA weight gradients) assume a fixed sequence of vector-memory instructions
+engine in gemm.hpp, the register-weight convs of gemm_ops.hip and the DMA weight gradients of gemm_ops.hip /
+wgrad_dma.hip) assume a fixed sequence of vector-memory instructions
 per tile.  A scratch spill is a vector-memory instruction the count does not know about, so every such kernel that
 the product path launches must have no private segment and no VGPR spills; the grouped-epilogue register-weight
 convs, which carry their epilogue state (store offsets, masks, output descriptor) across tiles, must not spill SGPRs

@@ -2,7 +2,7 @@
 HIP-event timing of s3od_attn_fwd and s3od_attn_bwd_qkv at the training shape (bs 16, N 4101) and the C5 shape
 (bs 4, N 16389), plus the relative difference of every output against the first setting.
 
-    python tools/attn_ab.py S3OD_ATTN_BWD_PP 1 0
+    python tools/attn_ab.py S3OD_ATTN_DMA 1 0
 """
 import os
 os.environ.setdefault("S3OD_AB", "1")   # knobs toggled per call (csrc/common.hpp S3OD_KNOB)

@@ -42,33 +42,28 @@ def hip(x, w, out):
 
 def kfit(M=65536, N=3072):
     """time vs K at fixed M, N: the intercept is the per-launch fixed cost (prologue / epilogue / tail), the slope the
-    main-loop rate; S3OD_EPI_PROBE=1 rows skip the epilogue stores"""
+    main-loop rate"""
     g = torch.Generator(device="cuda").manual_seed(0)
     for c in os.environ.get("CFGS", "5").split(","):
         os.environ["S3OD_GEMM_CFG"] = c
-        for probe in ("0", "1"):
-            os.environ["S3OD_EPI_PROBE"] = probe
-            pts = []
-            for K in (256, 768, 1536, 3072, 6144):
-                x = (torch.rand(M, K, device="cuda", generator=g) * 2 - 1).bfloat16()
-                w = (torch.rand(N, K, device="cuda", generator=g) * 2 - 1).bfloat16()
-                out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
-                f = lambda: lib()("s3od_linear_fwd", BF16, M, N, K, x, K, w, None, None, None, 0, None, N, None, 0, 0, out,
-                                  N, 0, None, N, 0, 0, 0, stream())
-                t = timeit(f, 10) * 1e6
-                th = timeit(lambda: torch.matmul(x, w.t(), out=out), 10) * 1e6 if probe == "0" else 0.0
-                pts.append((K, t, th))
-            n = len(pts)
-            for idx in (1, 2):
-                mk = sum(p[0] for p in pts) / n; mt = sum(p[idx] for p in pts) / n
-                b = sum((p[0] - mk) * (p[idx] - mt) for p in pts) / sum((p[0] - mk) ** 2 for p in pts)
-                a = mt - b * mk
-                who = f"cfg {c} probe {probe}" if idx == 1 else "hipBLASLt"
-                if idx == 2 and probe == "1":
-                    continue
-                print(f"M{M} N{N} {who:18s}: " + " ".join(f"K{p[0]}:{p[idx]:.1f}" for p in pts) +
-                      f" | fixed {a:.1f} us, {b * 64:.2f} us per 64-K ({2.0 * M * N * 64 / (b * 64) / 1e6:.0f} TF/s)", flush=True)
-        os.environ["S3OD_EPI_PROBE"] = "0"
+        pts = []
+        for K in (256, 768, 1536, 3072, 6144):
+            x = (torch.rand(M, K, device="cuda", generator=g) * 2 - 1).bfloat16()
+            w = (torch.rand(N, K, device="cuda", generator=g) * 2 - 1).bfloat16()
+            out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            f = lambda: lib()("s3od_linear_fwd", BF16, M, N, K, x, K, w, None, None, None, 0, None, N, None, 0, 0, out,
+                              N, 0, None, N, 0, 0, 0, stream())
+            t = timeit(f, 10) * 1e6
+            th = timeit(lambda: torch.matmul(x, w.t(), out=out), 10) * 1e6
+            pts.append((K, t, th))
+        n = len(pts)
+        for idx in (1, 2):
+            mk = sum(p[0] for p in pts) / n; mt = sum(p[idx] for p in pts) / n
+            b = sum((p[0] - mk) * (p[idx] - mt) for p in pts) / sum((p[0] - mk) ** 2 for p in pts)
+            a = mt - b * mk
+            who = f"cfg {c}" if idx == 1 else "hipBLASLt"
+            print(f"M{M} N{N} {who:18s}: " + " ".join(f"K{p[0]}:{p[idx]:.1f}" for p in pts) +
+                  f" | fixed {a:.1f} us, {b * 64:.2f} us per 64-K ({2.0 * M * N * 64 / (b * 64) / 1e6:.0f} TF/s)", flush=True)
 
 
 if __name__ == "__main__":

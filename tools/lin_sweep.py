@@ -109,7 +109,7 @@ def report(name, fl, t):
 
 if __name__ == "__main__":
     if os.environ.get("SWEEP") == "ab":
-        # same-process A/B of a per-call knob: KNOB=<env name>, positional values (e.g. S3OD_PP_DMA 0 1)
+        # same-process A/B of a per-call knob: KNOB=<env name>, positional values (e.g. S3OD_TAIL_SKINNY 0 1)
         knob = os.environ["KNOB"]
         for rnd in range(2):
             for val in sys.argv[1:]:

@@ -1,6 +1,5 @@
-"""A/B of the halo-tile 3x3 weight gradients at bs 16: the LDS-DMA kernel (default: producer-wave form) vs the
-register-staged one (S3OD_WGRAD_DMA=0) and the 4-wave LDS-DMA form (p0 = S3OD_WGD_PROD=0), knobs read per call,
-one process, interleaved rounds; results compared (dev tool).
+"""A/B of the halo-tile 3x3 weight gradients at bs 16: the LDS-DMA kernel (default) vs the register-staged one
+(S3OD_WGRAD_DMA=0), knob read per call, one process, interleaved rounds; results compared (dev tool).
 Shapes: upsample_2x.2 (1024^2, 64 -> 64), output_conv1 (512^2, 256 -> 128, ReLU'd input), mask heads (1024^2, 64 -> 96).
 
     python tools/wgrad_bench.py            # A/B, every shape
@@ -85,9 +84,8 @@ def main():
         fl = 2.0 * B * H * H * cin * cout * 9
         res = {}
         for rnd in range(1 if pmc else 3):
-            for knob in ("1",) if pmc else ("0", "1", "p0"):
-                os.environ["S3OD_WGRAD_DMA"] = "0" if knob == "0" else "1"   # p0: the 4-wave LDS-DMA kernel
-                os.environ["S3OD_WGD_PROD"] = "0" if knob == "p0" else "1"
+            for knob in ("1",) if pmc else ("0", "1"):
+                os.environ["S3OD_WGRAD_DMA"] = knob
                 dw = torch.zeros(cout, cin, 3, 3, device="cuda")
                 f = lambda: lib()("s3od_conv_wgrad", BF16, B, H, H, cin, H, H, cout, 3, 3, 1, 1, dy, x, relu, dw, ws, 0, None, 0, stream())
                 t = timeit(f)
@@ -98,11 +96,8 @@ def main():
                 print(f"{H}^2 {cin}->{cout} relu {relu} round {rnd} DMA={knob}: {t * 1e6:8.1f} us {fl / t / 1e12:7.1f} TF/s", flush=True)
         if pmc:
             continue
-        b = res["0"]
-        for k in ("1", "p0"):
-            a = res[k]
-            print(f"{H}^2 {k}: max |dma - staged| / max|staged| = {float((a - b).abs().max() / b.abs().max()):.3e}")
-    os.environ.pop("S3OD_WGD_PROD", None)
+        a, b = res["1"], res["0"]
+        print(f"{H}^2: max |dma - staged| / max|staged| = {float((a - b).abs().max() / b.abs().max()):.3e}")
     if pmc:
         return
     # upsample_2x.0 (ConvTranspose2d(128, 64, 4, 2, 1)) in its conv view: dy 512^2 x 128, x 1024^2 x 64
