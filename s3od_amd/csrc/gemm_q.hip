@@ -7,21 +7,36 @@
 // reaches 1450-1470 TF/s at 87 % MFMA-busy with 0.25 LDS instructions per MFMA (profiles/r06d_gemm_pmc.txt).
 // A 128x128 wave tile halves the fragment reads per MFMA (each A / B fragment feeds 8 MFMAs instead of 4).
 //
-// K loop (BK = 64 = two 32-deep k-steps, 64 MFMAs each per wave), two LDS stages of 64 KB (A 256 x 64 | B 256 x 64):
-//   k-step 0 of tile t:  read tile t's k-step-1 fragments (16 x ds_read_b128 / tr pairs) | 64 MFMAs
-//   k-step 1 of tile t:  vmcnt(0) (tile t+1 landed) + barrier  ->  LDS-DMA of tile t+2 into tile t's stage (its last
-//                        reads were the k-step-1 fragments, read before the barrier) | read tile t+1's k-step-0
-//                        fragments | 64 MFMAs
-// so a tile's DMA is issued two k-steps (128 MFMAs) before its wait, and the MFMAs of each k-step find their
-// fragments in registers (double-buffered by k-step).  One barrier per K tile.
-// Epilogue: the fp32 C tile is staged through the (free) K-stage LDS in two 128-row halves and handed to the same
+// K loop: a ring of four LDS stages, one 32-deep k-step (64 MFMAs per wave) each: A 256 x 64 B | B 256 x 64 B = 32 KB
+// (images and loaders: gemm.hpp KStep / QFrag).  K-step s computes from fragment buffer s & 1 and, INSIDE its MFMA
+// stream, reads the fragments of k-step s + 1 (stage (s + 1) & 3) into the other buffer and issues the LDS-DMA of
+// k-step s + 4 into its own stage s & 3:
+//   lgkmcnt(0)                  this k-step's fragments (read a whole block ago) are in
+//   MFMA 0-3
+//   vmcnt(16) + s_barrier       own pieces of k-step s + 1 landed; s + 2 and s + 3 (8 pieces per wave each) stay in
+//                               flight, so a stage has three k-steps = 192 MFMAs to arrive and the wait is never 0
+//                               (k-steps past the end of the K range are staged too, as zeros from the range
+//                               check and never computed, so the count holds in the prologue and the tail as well)
+//   MFMA 4-..                   two fragment reads per MFMA gap (one where both operands are ds_read_b64_tr pairs),
+//                               then one DMA piece every fourth gap
+//   RAW: a stage is read only behind the barrier that follows every wave's counted wait for its pieces of that stage.
+//   WAR: stage s & 3 is restaged behind the barrier of k-step s; its only reads (the fragments of k-step s, issued
+//        in block s - 1) are behind every wave's lgkmcnt(0) at the head of block s, ahead of that barrier.
+// The loop body is one pair of stages; fragment addresses are per-lane constants plus immediates, moved to the other
+// pair once per iteration.  One barrier per k-step.
+// Epilogue: the fp32 C tile is staged through the (free) ring LDS in two 128-row halves and handed to the same
 // block-level epilogue functors as the other kernels (NT = 256 threads).
 #include "gemm.hpp"
 
 namespace {
-constexpr int Q_THREADS = 256, Q_BM = 256, Q_BN = 256, Q_STAGE = (Q_BM + Q_BN) * 128, Q_LDT = Q_BN + 4;
-constexpr int Q_LDS = (2 * Q_STAGE > 128 * Q_LDT * 4) ? 2 * Q_STAGE : 128 * Q_LDT * 4;
+constexpr int Q_THREADS = 256, Q_BM = 256, Q_BN = 256, Q_IMG = 256 * 64, Q_STAGE = 2 * Q_IMG, Q_RING = 4, Q_LDT = Q_BN + 4;
+constexpr int Q_LDS = (Q_RING * Q_STAGE > 128 * Q_LDT * 4) ? Q_RING * Q_STAGE : 128 * Q_LDT * 4;
 static_assert(Q_LDS <= 160 * 1024, "q kernel LDS budget");
+template <int V> using IC = std::integral_constant<int, V>;
+// f(IC<0>) .. f(IC<N - 1>): a compile-time loop (a `#pragma unroll` loop around the barrier of a k-step stays rolled,
+// which would index the accumulators at run time)
+template <class F, int... I> DEV void q_seq(F& f, std::integer_sequence<int, I...>) { (f(IC<I>{}), ...); }
+template <int N, class F> DEV void q_for(F f) { q_seq(f, std::make_integer_sequence<int, N>{}); }
 }
 
 // lgkmcnt(0) as the builtin (vmcnt 63, expcnt 7 = no wait): unlike the inline-asm wait_lgkm0(), the waitcnt pass sees
@@ -30,8 +45,8 @@ DEV void q_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
 
 template <class LA, class LB, class EPI>
 __global__ void __launch_bounds__(Q_THREADS, 1) igemm_q_kernel(LA la, LB lb, EPI epi, int KTILES, int split, int group) {
-  typedef bf16 T;
   static_assert(LA::ROWS == 256 && LB::ROWS == 256 && LA::NIW == 8 && LB::NIW == 8, "q kernel: 256-row loaders on 4 waves");
+  static_assert(!LA::RELU && !LB::RELU, "q kernel: no ReLU-on-load (a VALU write of a fragment inside the MFMA stream)");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int wm = wave >> 1, wn = wave & 1;
@@ -41,81 +56,87 @@ __global__ void __launch_bounds__(Q_THREADS, 1) igemm_q_kernel(LA la, LB lb, EPI
     tile_of_block(group, mt, nt_);
     m0 = mt * Q_BM; n0 = nt_ * Q_BN;
   }
+  // split-K ranges stay in 64-deep K tiles (the ping-pong kernel's ranges: same partial sums per split); a tile is
+  // two k-steps, the second all zeros where K % 64 <= 32
   const int per = (KTILES + split - 1) / split;
   const int kt0 = blockIdx.z * per, kt1 = min(KTILES, kt0 + per);
-  const int nt = kt1 - kt0;
+  const int ks0 = 2 * kt0, n = 2 * (kt1 - kt0);
   epi.prepare(blockIdx.z);
-  la.setup(m0, tid);
-  lb.setup(n0, tid);
-  constexpr int NL = LA::NIW + LB::NIW;        // LDS-DMA instructions per wave per K tile
+  // K-steps at or past klim (the end of this block's K range) are zero-filled by the range check, so EVERY k-step
+  // issues its eight pieces and the counted wait is the same number in the prologue, in steady state and in the tail
+  const int klim = min(la.K, (ks0 + n) * 32);
+  KStep<LA> sa; KStep<LB> sb;
+  sa.setup(la, m0, tid, klim);
+  sb.setup(lb, n0, tid, klim);
+  QFrag<LA::KCL> qa; QFrag<LB::KCL> qb;
+  qa.init(smem, lane, wm);
+  qb.init(smem + Q_IMG, lane, wn);
   f32x4 acc[8][8];
 #pragma unroll
   for (int i = 0; i < 8; i++)
 #pragma unroll
     for (int j = 0; j < 8; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 fa[2][8], fb[2][8];
-  auto read_frags = [&](int buf, const char* stage, int kk) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) fa[buf][i] = Frag<T, LA::KCL, Q_BM>::read(stage, wm * 128 + i * 16, kk, lane);
-#pragma unroll
-    for (int j = 0; j < 8; j++) fb[buf][j] = Frag<T, LB::KCL, Q_BN>::read(stage + Q_BM * 128, wn * 128 + j * 16, kk, lane);
+  // fragment f of a k-step: B blocks 0-7, then A blocks 0-7; st01 = the stage's place in the current pair of stages
+  auto read_frag = [&](int buf, int st01, int f) {
+    if (f < 8) fb[buf][f] = qb.read(st01, f);
+    else fa[buf][f - 8] = qa.read(st01, f - 8);
   };
+  // DMA piece d of k-step ks into a stage: A pieces 0-3, then B pieces 0-3
+  auto dma_piece = [&](int ks, char* stage, int d) {
+    if (d < 4) sa.piece(la, ks, stage, d);
+    else sb.piece(lb, ks, stage + Q_IMG, d - 4);
+  };
+  // One k-step: ks = its index in K, stage = its own stage (restaged with k-step ks + 4), P = its place in its pair
+  // of stages (0: the next k-step's fragments are in this pair's second stage; 1: in the other pair's first stage,
+  // to which the fragment addresses are moved first: `flip` = +- 64 KB).
   // The MFMAs are inline asm with tied "+a" accumulators: with the builtin, the register allocator rotates the 64
   // accumulator tuples through VGPRs at the loop back-edge (180 v_accvgpr moves per K tile).  Inline asm is outside
   // the hazard recogniser, so the block covers its own hazards: s_nop 1 ahead of it (VALU write -> XDL SrcA/B read),
   // every fragment kept live to its end (no register of a fragment an in-flight MFMA still reads is reallocated
-  // inside the block) and s_nop 7 x 2 behind it (XDL SrcA/B/C read -> VALU / DS write of the same register).
-  auto mfmas = [&](int buf) {
-    if constexpr (LA::RELU) {
-#pragma unroll
-      for (int i = 0; i < 8; i++) fa[buf][i] = relu_frag(fa[buf][i]);
-    }
-    if constexpr (LB::RELU) {
-#pragma unroll
-      for (int j = 0; j < 8; j++) fb[buf][j] = relu_frag(fb[buf][j]);
-    }
-    asm volatile("s_nop 1");
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-      for (int j = 0; j < 8; j++)
-        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fb[buf][j]), "v"(fa[buf][i]));
-    asm volatile("s_nop 7\n\ts_nop 7" :: "v"(fa[buf][0]), "v"(fa[buf][1]), "v"(fa[buf][2]), "v"(fa[buf][3]),
-                 "v"(fa[buf][4]), "v"(fa[buf][5]), "v"(fa[buf][6]), "v"(fa[buf][7]), "v"(fb[buf][0]), "v"(fb[buf][1]),
-                 "v"(fb[buf][2]), "v"(fb[buf][3]), "v"(fb[buf][4]), "v"(fb[buf][5]), "v"(fb[buf][6]), "v"(fb[buf][7]));
-  };
-  auto issue = [&](int kt, char* stage) {
-    la.issue(kt, stage);
-    lb.issue(kt, stage + Q_BM * 128);
-  };
-  if (nt > 0) {
-    issue(kt0, smem);
-    if (nt > 1) { issue(kt0 + 1, smem + Q_STAGE); wait_vmcnt<NL>(); }
-    else wait_vmcnt<0>();
-    raw_barrier();
-    read_frags(0, smem, 0);
-    // the last tile is peeled: a loop body whose second k-step may or may not issue fragment reads makes the
-    // waitcnt pass merge both paths and wait (lgkmcnt 7..0) on the NEXT tile's fragment reads inside the MFMAs
-    for (int t = 0; t + 1 < nt; ++t) {
-      char* cur = smem + (t & 1) * Q_STAGE;
-      char* nxt = smem + ((t + 1) & 1) * Q_STAGE;
-      // k-step 0: tile t's k-step-1 fragments are read behind its 64 MFMAs (lgkmcnt(0) first: the k-step-0
-      // fragments, read 64 MFMAs ago, are in -- the counter cannot tell them from the 16 reads issued after them)
-      q_wait_lgkm0();
-      read_frags(1, cur, 1);
-      mfmas(0);
-      // k-step 1: tile t+1 landed (the only DMA in flight) -> barrier -> tile t+2 into this tile's stage
-      wait_vmcnt<0>();
-      q_wait_lgkm0();
-      raw_barrier();
-      if (t + 2 < nt) issue(kt0 + t + 2, cur);
-      read_frags(0, nxt, 0);
-      mfmas(1);
-    }
+  // inside the block), the first read into the other buffer behind MFMA 3 and the barrier (the previous block's
+  // MFMAs, which read that buffer, have all issued and read their sources by then), and s_nop 7 x 3 ahead of the
+  // accumulator reads of the epilogue.
+  constexpr int FPG = (LA::KCL || LB::KCL) ? 2 : 1;       // fragment reads per MFMA gap
+  constexpr int D0 = 4 + 16 / FPG + 4, DS = 4;            // first DMA gap, gaps between pieces
+  static_assert(D0 + 7 * DS < 64, "DMA pieces inside the block");
+  auto kstep = [&](auto PC, int ks, char* stage, int flip) __attribute__((always_inline)) {
+    constexpr int P = decltype(PC)::value;
+    if constexpr (P == 1) { qa.flip(flip); qb.flip(flip); }
     q_wait_lgkm0();
-    read_frags(1, smem + ((nt - 1) & 1) * Q_STAGE, 1);
-    mfmas(0);
-    mfmas(1);
+    asm volatile("s_nop 1");
+    q_for<64>([&](auto MC) __attribute__((always_inline)) {
+      constexpr int m = decltype(MC)::value, i = m >> 3, j = m & 7;
+      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[i][j]) : "v"(fb[P][j]), "v"(fa[P][i]));
+      if constexpr (m == 3) { wait_vmcnt<16>(); raw_barrier(); }
+      if constexpr (m >= 4 && m < 4 + 16 / FPG) {
+#pragma unroll
+        for (int u = 0; u < FPG; u++) read_frag(P ^ 1, P ^ 1, (m - 4) * FPG + u);
+      }
+      if constexpr (m >= D0 && (m - D0) % DS == 0 && (m - D0) / DS < 8) dma_piece(ks + 4, stage, (m - D0) / DS);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    asm volatile("" :: "v"(fa[P][0]), "v"(fa[P][1]), "v"(fa[P][2]), "v"(fa[P][3]),
+                 "v"(fa[P][4]), "v"(fa[P][5]), "v"(fa[P][6]), "v"(fa[P][7]), "v"(fb[P][0]), "v"(fb[P][1]),
+                 "v"(fb[P][2]), "v"(fb[P][3]), "v"(fb[P][4]), "v"(fb[P][5]), "v"(fb[P][6]), "v"(fb[P][7]));
+  };
+  if (n > 0) {
+    // prologue: four stages (24 pieces stay in flight behind stage 0), then stage 0's fragments
+#pragma unroll
+    for (int q = 0; q < Q_RING; q++)
+#pragma unroll
+      for (int d = 0; d < 8; d++) dma_piece(ks0 + q, smem + q * Q_STAGE, d);
+    wait_vmcnt<24>();
+    raw_barrier();
+#pragma unroll
+    for (int f = 0; f < 16; f++) read_frag(0, 0, f);
+    // one pair of stages (= one 64-deep K tile) per iteration; the pair alternates
+    int pair = 0, flip = 2 * Q_STAGE;
+    for (int s = 0; s < n; s += 2) {
+      kstep(IC<0>{}, ks0 + s, smem + pair, flip);
+      kstep(IC<1>{}, ks0 + s + 1, smem + pair + Q_STAGE, flip);
+      pair ^= 2 * Q_STAGE; flip = -flip;
+    }
   }
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");   // XDL write -> accumulator read (epilogue)
   vm_drain();

@@ -261,15 +261,18 @@ static int linear_dgrad_rows(int dtype, int M, int N, int K, const void* dy, lon
 }
 
 // The route of a linear weight gradient, shared by the slab query and the call: f(TileCfg, split-K factor, slab
-// floats).  Tile config: the 256x256 ping-pong kernel with split-K slabs for the large outputs (3072x768 441 -> 403 us,
-// 768x3072 457 -> 398, 2304x768 335 -> 308), 256x128 x 3 stages with fp32 atomics otherwise.  (The small outputs over
+// floats).  Tile config: a 256x256 kernel with split-K slabs for the large outputs -- the 4-wave kernel (gemm_q.hip),
+// whose ring of k-step stages beats the ping-pong kernel in every round of a same-process A/B over 65616 rows
+// (3072x768 348-411 -> 287-316 us, 768x3072 345-390 -> 273-278, 2304x768 269-289 -> 206-221;
+// profiles/gemm_q_ring_lin_ab.txt), same split factor and slabs, bit-identical partial sums -- and 256x128 x 3 stages
+// with fp32 atomics otherwise.  (The small outputs over
 // >= 64K rows are faster alone on the ping-pong kernel too -- tools/wgrad_sweep.py: 768x768 127 -> 110 us, 1024x768
 // 154 -> 144, 256x256 x 1M rows 283 -> 268; profiles/r05t_wgrad_sweep.txt -- but null in the step, where these run on
 // the side stream beside the data gradients: tools/ab_step.py medians 151.4 vs 151.0 ms.)
 // Slab floats (0: the fp32-atomic epilogue, no slab): the 256x256 kernels' split-K partials go to sp caller-owned
 // fp32 slabs [sp][Nout][Kin], summed by wgrad_reduce_kernel.
 template <typename T, class F> static int linear_wgrad_route(int Nout, int Kin, int rows, int split, F f) {
-  const int def = (long)Nout * Kin > 1024L * 1024 ? 5 : 0;
+  const int def = (long)Nout * Kin > 1024L * 1024 ? 6 : 0;
   return with_cfg<T, true>(def, false, [&](auto C) -> int {
     typedef decltype(C) CC;
     const int KTILES = cdiv(rows, KT<T>::BK);
