@@ -340,6 +340,22 @@ DEV void bil_coef(int o, int in, int out, int& i0, int& i1, float& w0, float& w1
   i1 = i0 + 1 < in ? i0 + 1 : in - 1;
   w1 = src - (float)i0; w0 = 1.f - w1;
 }
+// The same taps with the source coordinate taken exactly: src = ((2o + 1) in - out) / (2 out) as an integer
+// quotient and remainder, so w1 carries one rounding.  bil_coef's f32 `scale` and product leave the weights
+// off by up to ~2^-23 * in for a ratio that f32 does not hold (12 -> 25: outputs 3 * 2^-22 max|x| from the
+// float64 interpolation).  For the exact 2x ratio both give the same taps and weights (1/4, 3/4), which is
+// why the 2x kernels keep the cheaper float form.  (2 out + 1) * in must fit an int: in * out < 2^30.
+DEV void bil_coef_exact(int o, int in, int out, int& i0, int& i1, float& w0, float& w1) {
+  const int num = (2 * o + 1) * in - out, den = 2 * out;
+  i0 = 0; w1 = 0.f;
+  if (num > 0) {
+    i0 = num / den;
+    w1 = (float)(num - i0 * den) / (float)den;
+    if (i0 > in - 1) { i0 = in - 1; w1 = 0.f; }
+  }
+  i1 = i0 + 1 < in ? i0 + 1 : in - 1;
+  w0 = 1.f - w1;
+}
 
 template <typename T>
 __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int IH, int IW, int OH, int OW, int C) {
@@ -349,8 +365,8 @@ __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, 
   int c = i % C; long pix = i / C;
   int ox = pix % OW; long r = pix / OW; int oy = r % OH; int b = r / OH;
   int y0, y1, x0, x1; float wy0, wy1, wx0, wx1;
-  bil_coef(oy, IH, OH, y0, y1, wy0, wy1);
-  bil_coef(ox, IW, OW, x0, x1, wx0, wx1);
+  bil_coef_exact(oy, IH, OH, y0, y1, wy0, wy1);
+  bil_coef_exact(ox, IW, OW, x0, x1, wx0, wx1);
   const T* base = x + (long)b * IH * IW * C + c;
   float a[8], bb[8], cc[8], d[8], o[8];
   load8<T>(base + ((long)y0 * IW + x0) * C, a); load8<T>(base + ((long)y0 * IW + x1) * C, bb);
@@ -455,11 +471,11 @@ __global__ void bilinear_bwd_kernel(const T* __restrict__ dy, const float* __res
     return;
   }
   for (int oy = oy_lo; oy <= oy_hi; oy++) {
-    int a0, a1; float u0, u1; bil_coef(oy, IH, OH, a0, a1, u0, u1);
+    int a0, a1; float u0, u1; bil_coef_exact(oy, IH, OH, a0, a1, u0, u1);
     float wy = (a0 == iy ? u0 : 0.f) + (a1 == iy ? u1 : 0.f);
     if (wy == 0.f) continue;
     for (int ox = ox_lo; ox <= ox_hi; ox++) {
-      int c0, c1; float v0, v1; bil_coef(ox, IW, OW, c0, c1, v0, v1);
+      int c0, c1; float v0, v1; bil_coef_exact(ox, IW, OW, c0, c1, v0, v1);
       float wx = (c0 == ix ? v0 : 0.f) + (c1 == ix ? v1 : 0.f);
       if (wx == 0.f) continue;
       float d[8]; load8<T>(dy + (((long)b * OH + oy) * OW + ox) * C + c, d);

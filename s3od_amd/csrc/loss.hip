@@ -133,7 +133,7 @@ __global__ void loss_grad_kernel(const float* __restrict__ logits, const float* 
 }
 
 __global__ void loss_iou_grad_kernel(const float* d_iou_unit, const float* gscale, float* d_iou, int n) {
-  int i = threadIdx.x;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) d_iou[i] = (gscale ? *gscale : 1.f) * d_iou_unit[i];
 }
 
@@ -344,7 +344,7 @@ int s3od_mask_loss_bwd(const float* logits, const float* target, const float* co
     hipLaunchKernelGGL(ssim_grad_kernel, dim3(cdiv(W, ST), cdiv(H, ST), B * M), dim3(256), SSIM_GRAD_LDS, st, logits, target, coef,
                        gscale, dlogits, M, H, W, gauss11());
   }
-  hipLaunchKernelGGL(loss_iou_grad_kernel, dim3(1), dim3(64), 0, st, d_iou_unit, gscale, d_iou, B * M);
+  hipLaunchKernelGGL(loss_iou_grad_kernel, dim3(cdiv(B * M, 64)), dim3(64), 0, st, d_iou_unit, gscale, d_iou, B * M);
   return s3od_check_launch("mask_loss_bwd");
 }
 
