@@ -176,6 +176,11 @@ static WgradRoute conv_wgrad_route(int dtype, int B, int H, int W, int Cin, int 
   return generic;
 }
 
+// The gathers walk a K tile over at most three taps, so a conv needs 2 Cin >= BK (bf16: 32 channels, f32: 16): the forward
+// loader refuses anything narrower (buf_ok), and the gradients of such a conv -- whose own gathers read dy or x and
+// would run -- are refused with it, before anything is launched.
+static bool conv_cin_ok(int dtype, int Cin) { return 2 * Cin >= (dtype == S3OD_BF16 ? KT<bf16>::BK : KT<float>::BK); }
+
 extern "C" {
 
 // ---------------------------------------------------------------------------------- convs
@@ -210,6 +215,7 @@ int s3od_conv_dgrad(int dtype, int B, int H, int W, int Cin, int OH, int OW, int
                     const float* bias, const float* scale, const float* shift, int act, const void* res1,
                     const void* res2, void* dx, void* pre, double* stats, float* colsum, const void* wT, void* stream) {
   S3OD_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "conv_dgrad: channels %% 8");
+  S3OD_REQUIRE(conv_cin_ok(dtype, Cin), "conv_dgrad: Cin %d is below half a K tile: no forward conv of this shape runs", Cin);
   if (wT && KH == 4 && KW == 4 && stride == 2 && pad == 1 && H == 2 * OH && W == 2 * OW && Cout == 128 && Cin == 64 && !scale &&
       !shift && !res1 && !res2 && !pre && !stats && !colsum && (act == ACT_NONE || act == ACT_RELU) && convt_rw_ok(dtype, B, OH, OW))
     // ConvTranspose2d(128, 64, 4, 2, 1) forward (upsample_2x.0): the register-weight sub-pixel kernel; wT =
@@ -277,6 +283,7 @@ int s3od_conv_wgrad(int dtype, int B, int H, int W, int Cin, int OH, int OW, int
                     int stride, int pad, const void* dy, const void* x, int relu_x, float* dw, float* ws, int split,
                     float* slab, long slab_bytes, void* stream) {
   S3OD_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0, "conv_wgrad: channels %% 8");
+  S3OD_REQUIRE(conv_cin_ok(dtype, Cin), "conv_wgrad: Cin %d is below half a K tile: no forward conv of this shape runs", Cin);
   ConvGeo g{}; g.B = B; g.SH = H; g.SW = W; g.SC = Cin; g.RH = OH; g.RW = OW; g.KH = KH; g.KW = KW; g.s = stride; g.p = pad;
   const int NPIX = B * OH * OW, M = Cout, N = KH * KW * Cin;
   hipStream_t st = (hipStream_t)stream;

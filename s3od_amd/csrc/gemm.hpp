@@ -267,13 +267,15 @@ struct TapWalk {
     if (++tw == TW) { tw = 0; th++; }
     return true;
   }
-  // generic (SC % BK != 0, 2 SC >= BK): advance by BK channels, a tile spans taps tap and tap+1
+  // generic (SC % BK != 0, 2 SC >= BK): advance by BK channels; a tile starting at channel c0 < SC covers channels up to
+  // c0 + BK - 1 < 3 SC, i.e. taps tap, tap+1 and -- for SC < BK, when c0 + BK > 2 SC (bf16 SC 40: c0 24 or 32) -- tap+2
   DEV void step_any(int kt, int BK, int SC, int TW) {
     if (kt != nk) { int k = kt * BK; tap = k / SC; c0 = k - tap * SC; th = tap / TW; tw = tap - th * TW; }
     else { c0 += BK; while (c0 >= SC) { c0 -= SC; tap++; if (++tw == TW) { tw = 0; th++; } } }
     nk = kt + 1;
   }
   DEV void next_tap(int TW, int& th1, int& tw1) const { tw1 = tw + 1; th1 = th; if (tw1 == TW) { tw1 = 0; th1++; } }
+  DEV static void tap_after(int TW, int th1, int tw1, int& th2, int& tw2) { tw2 = tw1 + 1; th2 = th1; if (tw2 == TW) { tw2 = 0; th2++; } }
 };
 
 // conv forward A operand: rows = output pixels (b,oy,ox) of RH x RW, k = tap*SC + c
@@ -314,15 +316,15 @@ template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Con
     const auto rs = make_rsrc(xb, nb);
     if (g.SC % BK) {                 // channels not a multiple of BK: per-lane tap (rare shapes)
       tw.step_any(kt, BK, g.SC, g.KW);
-      int th1, tw1; tw.next_tap(g.KW, th1, tw1);
+      int th1, tw1, th2, tw2; tw.next_tap(g.KW, th1, tw1); TapWalk::tap_after(g.KW, th1, tw1, th2, tw2);
 #pragma unroll
       for (int i = 0; i < NIW; i++) {
         int c = tw.c0 + kl[i];
-        bool wr = c >= g.SC;
-        int th = wr ? th1 : tw.th, tww = wr ? tw1 : tw.tw;
+        const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
+        int th = wr == 2 ? th2 : wr ? th1 : tw.th, tww = wr == 2 ? tw2 : wr ? tw1 : tw.tw;
         int iy = iy0[i] + th, ix = ix0[i] + tww;
-        bool ok = tw.tap + (int)wr < g.KH * g.KW && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
-        int off = pix0[i] - kl[i] + (th * g.SW + tww) * g.SC + (wr ? c - g.SC : c);
+        bool ok = tw.tap + wr < g.KH * g.KW && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
+        int off = pix0[i] - kl[i] + (th * g.SW + tww) * g.SC + (c - wr * g.SC);
         sk(i, rs, ok ? (unsigned)off * (unsigned)sizeof(T) : BUF_OOB);
       }
       return;
@@ -429,15 +431,15 @@ template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradA {
     const int TW = g.ntw > 0 ? g.ntw : 1;
     if (g.SC % BK) {                 // channels not a multiple of BK: per-lane tap (rare shapes)
       tw.step_any(kt, BK, g.SC, TW);
-      int th1, tw1; tw.next_tap(TW, th1, tw1);
+      int th1, tw1, th2, tw2; tw.next_tap(TW, th1, tw1); TapWalk::tap_after(TW, th1, tw1, th2, tw2);
 #pragma unroll
       for (int i = 0; i < NIW; i++) {
         int c = tw.c0 + kl[i];
-        bool wr = c >= g.SC;
-        int th = wr ? th1 : tw.th, tww = wr ? tw1 : tw.tw;
+        const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
+        int th = wr == 2 ? th2 : wr ? th1 : tw.th, tww = wr == 2 ? tw2 : wr ? tw1 : tw.tw;
         int sy = ry[i] - th, sx = rx[i] - tww;
-        bool ok = tw.tap + (int)wr < g.nth * g.ntw && (unsigned)sy < (unsigned)g.SH && (unsigned)sx < (unsigned)g.SW;
-        int off = pix0[i] - kl[i] - (th * g.SW + tww) * g.SC + (wr ? c - g.SC : c);
+        bool ok = tw.tap + wr < g.nth * g.ntw && (unsigned)sy < (unsigned)g.SH && (unsigned)sx < (unsigned)g.SW;
+        int off = pix0[i] - kl[i] - (th * g.SW + tww) * g.SC + (c - wr * g.SC);
         sk(i, rs, ok ? (unsigned)off * (unsigned)sizeof(T) : BUF_OOB);
       }
       return;
@@ -483,19 +485,23 @@ template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradB {
   template <class SK> DEV void issue_to(int kt, SK sk) {
     const auto rs = make_rsrc(w, bytes());
     const int TW = g.ntw > 0 ? g.ntw : 1;
-    if (g.SC % BK) {                 // a tile spans taps tap / tap+1 (rows c0+kr >= SC wrap)
+    if (g.SC % BK) {                 // a tile spans taps tap .. tap+2 (rows c0+kr >= SC, >= 2 SC wrap)
       tw.step_any(kt, BK, g.SC, TW);
-      int th1, tw1; tw.next_tap(TW, th1, tw1);
+      int th1, tw1, th2, tw2; tw.next_tap(TW, th1, tw1); TapWalk::tap_after(TW, th1, tw1, th2, tw2);
       const int kh = g.kh0 + g.s * tw.th, kw = g.kw0 + g.s * tw.tw;
       const int kh1 = g.kh0 + g.s * th1, kw1 = g.kw0 + g.s * tw1;
-      const bool tv0 = tw.tap < g.nth * g.ntw, tv1 = tw.tap + 1 < g.nth * g.ntw;
+      const int kh2 = g.kh0 + g.s * th2, kw2 = g.kw0 + g.s * tw2;
+      const int nt = g.nth * g.ntw;
+      const bool tv0 = tw.tap < nt, tv1 = tw.tap + 1 < nt, tv2 = tw.tap + 2 < nt;
       const unsigned u0 = (unsigned)((((long)tw.c0 * g.KH + kh) * g.KW + kw) * NC * sizeof(T));
       const unsigned u1 = (unsigned)((((long)(tw.c0 - g.SC) * g.KH + kh1) * g.KW + kw1) * NC * sizeof(T));
+      const unsigned u2 = (unsigned)((((long)(tw.c0 - 2 * g.SC) * g.KH + kh2) * g.KW + kw2) * NC * sizeof(T));
 #pragma unroll
       for (int i = 0; i < NIW; i++) {
-        bool wr = tw.c0 + kr[i] >= g.SC;
-        bool ok = cv[i] && (wr ? tv1 : tv0);
-        sk(i, rs, ok ? lo[i] + (wr ? u1 : u0) : BUF_OOB);
+        const int c = tw.c0 + kr[i];
+        const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
+        bool ok = cv[i] && (wr == 2 ? tv2 : wr ? tv1 : tv0);
+        sk(i, rs, ok ? lo[i] + (wr == 2 ? u2 : wr ? u1 : u0) : BUF_OOB);
       }
       return;
     }
