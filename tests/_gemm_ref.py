@@ -1,6 +1,9 @@
-"""Shared by test_gemm_ref_cpu.py, test_gpu_linear_edges.py and test_gpu_conv_generic.py: float64 references of the
-implicit-GEMM entry points (csrc/gemm.hpp through linear_ops.hip / conv_ops.hip), a per-element error cap derived from
-the arithmetic, an f32 emulation of the most error-prone correct kernel, and NaN-poisoned buffers.
+"""Shared by test_gemm_ref_cpu.py, test_gpu_linear_edges.py, test_gpu_conv_generic.py, test_gpu_conv_rw_edges.py and
+test_gpu_conv_wgrad_edges.py: float64 references of the GEMM and conv entry points (csrc/gemm.hpp through linear_ops.hip
+/ conv_ops.hip, and the hand-pipelined kernels of gemm_ops.hip / wgrad_dma.hip they route to), a per-element error cap
+derived from the arithmetic, an f32 emulation of the most error-prone correct kernel, NaN-poisoned buffers, and (at the
+end) the exact integer mode and the tile schedules of the persistent kernels.  The references compute on the device of
+their inputs (wide(t, device)); check() compares where the reference lives.
 
 Reference.  The operands are the values the kernel saw (bf16 or f32, widened to double).  The epilogue restates EpiStd:
     pre = acc + bias ;  v = pre * scale + shift ;  out = act(v) (+ res1) (+ res2)
@@ -43,9 +46,10 @@ QSCALE = 0.125 * 1.4426950408889634      # S3OD_QSCALE (csrc/common.hpp), an f32
 QSCALE = float(torch.tensor(QSCALE, dtype=torch.float32))
 
 
-def wide(t):
-    """the exact values a kernel saw, as float64 on the CPU"""
-    return None if t is None else t.detach().to("cpu", torch.float64)
+def wide(t, device="cpu"):
+    """the exact values a kernel saw, as float64 on the CPU -- or on `device`: the references below compute where their
+    inputs live, so a large case runs its float64 contractions on the GPU"""
+    return None if t is None else t.detach().to(device, torch.float64)
 
 
 # ------------------------------------------------------------------------------------------------ poisoned buffers
@@ -169,6 +173,7 @@ def finish(acc, S, kc, dtype, out_f32=False, bias=None, scale=None, shift=None, 
     else:
         r.t_pre = eps + BF * pre.abs() if bf else r.t_pre32
     r.pre_lin, r.pre, r.v, r.out = pre_lin, pre, v, out
+    r.S = S
     return r
 
 
@@ -274,6 +279,60 @@ def conv_cols(x, KH, KW, stride, pad):
     return c.view(B, C, KH * KW, -1).permute(0, 3, 2, 1).reshape(-1, KH * KW * C)
 
 
+PER_TAP = False               # test hook: take the per-tap matmul forms on the CPU too (test_gemm_ref_cpu.py)
+
+
+def _taps(x, w, stride, pad, OH, OW):
+    """padded NHWC x and, per tap, the [B, OH, OW, Cin] view of the pixels that tap reads"""
+    KH, KW = w.shape[2:]
+    xp = F.pad(x.permute(0, 2, 3, 1), (0, 0, pad, pad + stride, pad, pad + stride))
+    for kh in range(KH):
+        for kw in range(KW):
+            yield kh, kw, xp[:, kh:kh + stride * (OH - 1) + 1:stride, kw:kw + stride * (OW - 1) + 1:stride]
+
+
+def conv2d64(x, w, stride=1, pad=0):
+    """float64 conv2d; off the CPU (no float64 convolution there) one matmul per tap"""
+    if x.device.type == "cpu" and not PER_TAP:
+        return F.conv2d(x, w, stride=stride, padding=pad)
+    B, _, H, W = x.shape
+    Cout, _, KH, KW = w.shape
+    OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+    out = torch.zeros(B, OH, OW, Cout, dtype=x.dtype, device=x.device)
+    for kh, kw, v in _taps(x, w, stride, pad, OH, OW):
+        out += v @ w[:, :, kh, kw].T
+    return out.permute(0, 3, 1, 2)
+
+
+def conv_transpose2d64(dy, w, stride, pad, hw):
+    """float64 data gradient of conv2d(., w [Cout, Cin, KH, KW]) onto an hw = (H, W) input"""
+    H, W = hw
+    B, Cout, OH, OW = dy.shape
+    _, Cin, KH, KW = w.shape
+    if dy.device.type == "cpu" and not PER_TAP:
+        op = (H - ((OH - 1) * stride - 2 * pad + KH), W - ((OW - 1) * stride - 2 * pad + KW))
+        return F.conv_transpose2d(dy, w, stride=stride, padding=pad, output_padding=op)
+    buf = torch.zeros(B, max((OH - 1) * stride + KH, pad + H), max((OW - 1) * stride + KW, pad + W), Cin, dtype=dy.dtype,
+                      device=dy.device)
+    d = dy.permute(0, 2, 3, 1)
+    for kh in range(KH):
+        for kw in range(KW):
+            buf[:, kh:kh + stride * (OH - 1) + 1:stride, kw:kw + stride * (OW - 1) + 1:stride] += d @ w[:, :, kh, kw]
+    return buf[:, pad:pad + H, pad:pad + W].permute(0, 3, 1, 2)
+
+
+def conv2d_weight64(x, wshape, dy, stride, pad):
+    if x.device.type == "cpu" and not PER_TAP:
+        return torch.nn.grad.conv2d_weight(x, wshape, dy, stride=stride, padding=pad)
+    Cout, Cin, KH, KW = wshape
+    OH, OW = dy.shape[2:]
+    d = dy.permute(0, 2, 3, 1).reshape(-1, Cout).T.contiguous()
+    dw = torch.zeros(KH, KW, Cout, Cin, dtype=x.dtype, device=x.device)
+    for kh, kw, v in _taps(x, torch.empty(0, 0, KH, KW), stride, pad, OH, OW):
+        dw[kh, kw] = d @ v.reshape(-1, Cin)
+    return dw.permute(2, 3, 0, 1)
+
+
 def ref_conv(kind, x, w, dy=None, stride=1, pad=0, relu_in=False, hw=None, dw0=None, dtype="f32", emu=False, **epi):
     """float64 reference of one conv call on NCHW doubles; w is [Cout, Cin, KH, KW] (the conv view).
       "fwd":   conv2d(relu?(x), w)                      -> Ref over [B OH OW, Cout] (NHWC rows)
@@ -284,8 +343,8 @@ def ref_conv(kind, x, w, dy=None, stride=1, pad=0, relu_in=False, hw=None, dw0=N
     if relu_in and x is not None:
         x = x.clamp_min(0)
     if kind == "fwd":
-        acc = _nhwc2d(F.conv2d(x, w, stride=stride, padding=pad))
-        S = _nhwc2d(F.conv2d(x.abs(), w.abs(), stride=stride, padding=pad))
+        acc = _nhwc2d(conv2d64(x, w, stride, pad))
+        S = _nhwc2d(conv2d64(x.abs(), w.abs(), stride, pad))
         r = finish(acc, S, KH * KW * Cin, dtype, **epi)
         if emu:
             r.emu_pre, _, r.emu_out = epilogue(chain(conv_cols(x, KH, KW, stride, pad), w.permute(2, 3, 1, 0).reshape(-1, Cout)),
@@ -298,7 +357,8 @@ def ref_conv(kind, x, w, dy=None, stride=1, pad=0, relu_in=False, hw=None, dw0=N
         ct = lambda a, b: F.conv_transpose2d(a, b, stride=stride, padding=pad, output_padding=op)
         # a parity class has at most ceil(KH / s) ceil(KW / s) taps of Cout channels
         kc = -(-KH // stride) * -(-KW // stride) * Cout
-        r = finish(_nhwc2d(ct(dy, w)), _nhwc2d(ct(dy.abs(), w.abs())), kc, dtype, **epi)
+        ct64 = lambda a, b: conv_transpose2d64(a, b, stride, pad, hw)
+        r = finish(_nhwc2d(ct64(dy, w)), _nhwc2d(ct64(dy.abs(), w.abs())), kc, dtype, **epi)
         if emu:
             dy32, w32 = dy.float(), w.float()
             acc = torch.zeros(dy.shape[0], Cin, H, W, dtype=torch.float32)
@@ -311,7 +371,7 @@ def ref_conv(kind, x, w, dy=None, stride=1, pad=0, relu_in=False, hw=None, dw0=N
             r.emu_pre, _, r.emu_out = epilogue(_nhwc2d(acc), **_epi_only(epi))
         return r
     assert kind == "wgrad"
-    g = lambda a, b: torch.nn.grad.conv2d_weight(a, w.shape, b, stride=stride, padding=pad)
+    g = lambda a, b: conv2d_weight64(a, w.shape, b, stride, pad)
     npix = dy.shape[0] * dy.shape[2] * dy.shape[3]
     r = finish(g(x, dy).reshape(Cout, -1), g(x.abs(), dy.abs()).reshape(Cout, -1), npix, "f32", res1=dw0.reshape(Cout, -1), **epi)
     if emu:
@@ -331,9 +391,10 @@ def ratio(got, ref, t, skip=None):
 def check(got, ref, t, emu=None, skip=None, label=""):
     """1. every element finite; 2. max |got - ref| / t <= 1; 3. (emu given: f32 outputs) that ratio <= MARGIN x the
     emulation's.  Prints the worst ratio and its index; returns (kernel ratio, emulation ratio or None)."""
-    g = got.detach().to("cpu", torch.float64)
+    g = got.detach().to(ref.device, torch.float64)       # a device-side reference is compared where it lives
     ref = ref.reshape(g.shape)
     t = t.expand_as(ref) if t.dim() else t
+    emu = None if emu is None else emu.to(ref.device)
     bad = int((~torch.isfinite(g)).sum())
     assert bad == 0, f"{label}: {bad} of {g.numel()} elements not finite (never written, or poison read)"
     if skip is not None:
@@ -359,3 +420,87 @@ def check_token_rows(full, ref, t, B, P, prefix, emu=None, label=""):
     f = full.detach().cpu()
     assert bool(torch.isnan(f[keep]).all()), f"{label}: a prefix row was written"
     return check(f[rows], ref, t, emu, label=label)
+
+
+# ------------------------------------------------------------------------------------------------ fused mask heads
+def ref_heads(x, w1, b1, w2, b2, dtype="bf16"):
+    """s3od_mask_heads_fwd on NCHW float64 x: h = relu(conv3x3(x, w1 [32 NM, 64, 3, 3]) + b1), stored in `dtype` (hsave);
+    logit_k = b2[k] + sum_j h[32 k + j] w2[k, j] from the UNROUNDED h.  Returns (Ref of h over [B H W, 32 NM],
+    logits [B, NM, H, W], their cap).  With t_h the cap of the f32 h (ReLU is 1-Lipschitz, so the cap of v bounds it and
+    nothing is skipped): t = sum_j t_h |w2| + (32 + 8) 2^-23 sum_j |h w2| + 2^-23 |b2|."""
+    B, _, H, W = x.shape
+    NM = w2.shape[0]
+    rh = ref_conv("fwd", x, w1, stride=1, pad=1, dtype=dtype, bias=b1, act=ACT_RELU)
+    t_h = rh.t_sum - U * rh.out.abs()                      # the cap of v: the ReLU adds no rounding
+    h, t_h = rh.out.view(B, H, W, NM, 32), t_h.view(B, H, W, NM, 32)
+    logit = (h * w2).sum(-1) + b2
+    t = (t_h * w2.abs()).sum(-1) + (32 + 8) * U * (h * w2).abs().sum(-1) + U * b2.abs()
+    return rh, logit.permute(0, 3, 1, 2), t.permute(0, 3, 1, 2)
+
+
+# ------------------------------------------------------------------------------------------------ exact mode
+# Operands are small integers held in bf16, so every product and partial sum is an integer: exact in f32 below 2^24 and
+# in a bf16 output up to 256, whatever the summation order.  A correct kernel then matches the float64 reference bit for
+# bit, and ONE missing or doubled product is a mismatch -- at any K, where the worst-case cap (K + 8) 2^-23 S of the
+# random mode has long outgrown a single product (weight gradients over 10^4 .. 10^5 pixels).
+F32_EXACT, BF16_EXACT = 2.0 ** 24, 256.0
+
+
+def ints(shape, seed, p=0.5, device=None, dtype=torch.bfloat16):
+    """values in {-1, 0, 1}, non-zero with probability p, random signs"""
+    g = torch.Generator(device=device or DEVICE).manual_seed(seed)
+    u = torch.rand(shape, generator=g, device=device or DEVICE)
+    return (torch.where(u < p / 2, -1.0, 0.0) + torch.where(u > 1 - p / 2, 1.0, 0.0)).to(dtype)
+
+
+def small_ints(shape, seed, lo=-3, hi=3, device=None, dtype=torch.float32):
+    g = torch.Generator(device=device or DEVICE).manual_seed(seed)
+    return torch.randint(lo, hi + 1, shape, generator=g, device=device or DEVICE).to(dtype)
+
+
+def assert_exact_domain(f32_sums=(), bf16_values=()):
+    """the bounds under which exact mode is exact, asserted on float64 reference quantities: every f32 partial sum is
+    bounded by the sum of the absolute terms (< 2^24), every value stored as bf16 by 256"""
+    for s in f32_sums:
+        assert float(s.abs().max()) < F32_EXACT, float(s.abs().max())
+    for v in bf16_values:
+        assert float(v.abs().max()) <= BF16_EXACT, float(v.abs().max())
+
+
+def check_exact(got, ref, label=""):
+    """every element finite and EQUAL to the float64 reference (torch.equal of the values); prints the mismatch count"""
+    g = got.detach().to(ref.device, torch.float64)
+    ref = ref.reshape(g.shape)
+    bad = int((~torch.isfinite(g)).sum())
+    assert bad == 0, f"{label}: {bad} of {g.numel()} elements not finite (never written, or poison read)"
+    ne = g != ref
+    n = int(ne.sum())
+    at = tuple(int(i) for i in torch.unravel_index(ne.double().argmax(), ne.shape)) if n else ()
+    print(f"[{label}] exact: {n} of {g.numel()} elements differ" + (f", first at {at}: got {float(g[at])}, ref {float(ref[at])}" if n else ""))
+    assert n == 0 and torch.equal(g, ref), f"{label}: {n} of {g.numel()} elements differ from the exact reference, first at {at}"
+
+
+# ------------------------------------------------------------------------------------------------ tile schedules
+def rw_schedule(T, C):
+    """Restates the persistent register-weight kernels (gemm_ops.hip): nwg = min(max(T, 8), C) workgroups; XCD x =
+    blockIdx % 8 owns tiles [T x / 8, T (x + 1) / 8) and its workgroups stride through that range.  Returns the tile
+    list of every workgroup."""
+    nwg = min(max(T, 8), C)
+    out = []
+    for blk in range(nwg):
+        xcd, wi = blk & 7, blk >> 3
+        wpx = (nwg + 7 - xcd) >> 3
+        out.append(list(range(T * xcd // 8 + wi, T * (xcd + 1) // 8, wpx)))
+    return out
+
+
+def wgrad_schedule(T, C, nblk):
+    """Restates the weight-gradient launchers: wpc = max(1, min(T, C // nblk)) workgroups per channel block, workgroup wi
+    owns the contiguous tiles [T wi / wpc, T (wi + 1) / wpc).  Returns (wpc, tile list per workgroup)."""
+    wpc = max(1, min(T, max(1, C // nblk)))
+    return wpc, [list(range(T * wi // wpc, T * (wi + 1) // wpc)) for wi in range(wpc)]
+
+
+def crosses_image(sched, tiles_per_image):
+    """some workgroup's tiles come from two images (its buffer descriptor is rebased mid-range)"""
+    return any(len({t // tiles_per_image for t in tl}) > 1 for tl in sched)

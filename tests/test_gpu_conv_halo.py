@@ -72,7 +72,8 @@ def test_rw_grouped_epilogue_bit_identical(gb):
     to S3OD_RW_GB=0.  The masked data gradients (64 and 96 input channels) run ungrouped whatever the knob (their
     grouped instances spilled): checked unchanged under it; column sums to fp32 summation order."""
     from s3od_amd._lib import lib, stream
-    B, H, W = 3, 37, 70                                    # ragged: partial tiles, several tiles per workgroup
+    B, H, W = 3, 37, 70                                    # ragged: partial tiles; 45 tiles = one per workgroup on 256 CUs
+    # (several tiles per workgroup, the ring's steady state: test_gpu_conv_rw_edges.py)
     g = torch.Generator(device="cuda").manual_seed(11)
     x = torch.randn(B, H, W, 64, device="cuda", generator=g).bfloat16()
     wp = (torch.randn(64, 3, 3, 64, device="cuda", generator=g) * 0.06).bfloat16()
@@ -111,7 +112,7 @@ def test_rw_grouped_epilogue_bit_identical(gb):
             assert float((a - b).abs().max()) <= 1e-4 * float(b.abs().max()) + 1e-3, i
 
 
-@pytest.mark.parametrize("B,H,W", [(2, 50, 41), (3, 37, 70)])   # ragged; the second: several tiles per workgroup
+@pytest.mark.parametrize("B,H,W", [(2, 50, 41), (3, 37, 70)])   # ragged; 28 / 45 tiles: one per workgroup on 256 CUs
 def test_mask_heads_fwd_halo(B, H, W):
     from s3od_amd._lib import lib, stream
     NM = 3
@@ -137,7 +138,8 @@ def test_mask_heads_fwd_halo(B, H, W):
 def test_conv_wgrad_halo(cout, B, H, W, relu):
     """3x3 s1 weight gradient (halo-tile kernel for Cin 64 -> Cout 64 / 96) vs torch's conv2d_weight of
     the same bf16 operands, accumulated into an existing gradient (+=).  H % 8 == 0 and W % 32 == 0 with Cout 64
-    take the LDS-DMA kernel (csrc/wgrad_dma.hip: every border case, one-tile images, several images per workgroup;
+    take the LDS-DMA kernel (csrc/wgrad_dma.hip: every border case, one-tile images; at most 12 tiles, so one tile per
+    workgroup on 256 CUs -- several tiles and images per workgroup: test_gpu_conv_wgrad_edges.py;
     Cout 96 as two 64-channel blocks, the second padded); the ragged shapes the register-staged one."""
     from s3od_amd._lib import lib, stream
     g = torch.Generator(device="cuda").manual_seed(cout + H)
