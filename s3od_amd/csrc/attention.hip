@@ -16,8 +16,12 @@
 //     P = exp2(acc) is ONE v_exp per score;
 //   * lazy rescaling: m only moves when some score exceeds it by > 2^8 (wave-uniform branch);
 //   * the row sum l comes out of the matrix core: l += 1^T P^T (one extra MFMA per 32 keys).
-// K/V tiles of 64 keys are register-staged into double-buffered LDS (one barrier per tile).
+// K/V tiles of 64 keys go into double-buffered LDS (one barrier per tile): by LDS-DMA (bf16 default) or staged
+// through registers (f32; bf16 with S3OD_ATTN_DMA=0).  Both staging forms run the same per-tile body.
 // T=float runs the exact online softmax on v_mfma_f32_16x16x4_f32 (strict-parity path).
+//
+// Backward: bf16 on v_mfma_f32_32x32x16_bf16 (attn_bwd_dkdv32_kernel, attn_bwd_dq32_kernel); f32 on
+// v_mfma_f32_16x16x4_f32 (attn_bwd_dkdv_kernel, attn_bwd_dq_kernel: the strict-parity path only, no bf16 instance).
 #include "common.hpp"
 #include <type_traits>
 
@@ -53,16 +57,30 @@ DEV __amdgpu_buffer_rsrc_t attn_rsrc(const void* p, unsigned long bytes) {
   return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)(unsigned)bytes, 0x00020000);
 }
 
-template <typename T> struct Stage {
+// Register staging of one 64-key K / V tile (the forward without LDS-DMA): load() from global memory into registers,
+// store() into the TileL images.  The two loads share nothing, so each T has its own.
+template <typename T> struct StageRegs {
   static constexpr int CH = 64 * 64 * sizeof(T) / 16 / 256;   // 16-B chunks per thread per tile
+  static constexpr int CPR = 64 * sizeof(T) / 16;             // chunks per row
   uint4 k[CH], v[CH];
-  DEV void load(const T* K, const T* V, int key0, int N, int tid) {
-    constexpr int CPR = 64 * sizeof(T) / 16;
+  DEV void store(char* ks, char* vs, int tid) {
+#pragma unroll
+    for (int i = 0; i < CH; i++) {
+      int c = tid + 256 * i;
+      int key = c / CPR, byte = (c % CPR) * 16;
+      *(uint4*)(ks + TileL<T>::krow(key, byte)) = k[i];
+      *(uint4*)(vs + TileL<T>::vrow(key, byte)) = v[i];
+    }
+  }
+};
+template <typename T> struct Stage;
+template <> struct Stage<float> : StageRegs<float> {
+  DEV void load(const float* K, const float* V, int key0, int N, int tid) {
     if (key0 + 64 <= N) {             // whole tile in range (uniform): no per-key selects
 #pragma unroll
       for (int i = 0; i < CH; i++) {
         const int c = tid + 256 * i;
-        const long o = (long)(key0 + c / CPR) * 64 + (c % CPR) * (16 / sizeof(T));
+        const long o = (long)(key0 + c / CPR) * 64 + (c % CPR) * 4;
         k[i] = *(const uint4*)(K + o);
         v[i] = *(const uint4*)(V + o);
       }
@@ -71,36 +89,34 @@ template <typename T> struct Stage {
 #pragma unroll
     for (int i = 0; i < CH; i++) {
       int c = tid + 256 * i;
-      int key = key0 + c / CPR, col = (c % CPR) * (16 / sizeof(T));
+      int key = key0 + c / CPR, col = (c % CPR) * 4;
       bool ok = key < N;
       k[i] = ok ? *(const uint4*)(K + (long)key * 64 + col) : make_uint4(0, 0, 0, 0);
       v[i] = ok ? *(const uint4*)(V + (long)key * 64 + col) : make_uint4(0, 0, 0, 0);
     }
   }
-  // bf16: the same chunks by buffer loads -- per-thread byte offsets fixed, the tile's key offset on the scalar unit,
-  // keys >= N read zeros by the range check: no per-tile address or select VALU (the global-pointer form spent ~80
-  // VALU per tile on 64-bit addresses and tail selects beside 36 MFMAs)
-  DEV void load_buf(__amdgpu_buffer_rsrc_t rk, __amdgpu_buffer_rsrc_t rv, const unsigned (&vo)[CH], int key0) {
-    const int so = key0 * 64 * (int)sizeof(T);
+};
+// bf16: the same chunks by buffer loads -- per-thread byte offsets fixed, the tile's key offset on the scalar unit,
+// keys >= N read zeros by the range check: no per-tile address or select VALU (the global-pointer form spent ~80
+// VALU per tile on 64-bit addresses and tail selects beside 36 MFMAs)
+template <> struct Stage<bf16> : StageRegs<bf16> {
+  __amdgpu_buffer_rsrc_t rk, rv;
+  unsigned vo[CH];
+  DEV void init(const bf16* K, const bf16* V, int N, int tid) {
+    rk = attn_rsrc(K, (unsigned long)N * 128);
+    rv = attn_rsrc(V, (unsigned long)N * 128);
+#pragma unroll
+    for (int i = 0; i < CH; i++) {
+      const int c = tid + 256 * i;
+      vo[i] = (unsigned)((c / CPR) * 128 + (c % CPR) * 16);
+    }
+  }
+  DEV void load(int key0) {
+    const int so = key0 * 128;
 #pragma unroll
     for (int i = 0; i < CH; i++) {
       k[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rk, vo[i], so, 0));
       v[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rv, vo[i], so, 0));
-    }
-  }
-  DEV static unsigned chunk_off(int tid, int i) {
-    constexpr int CPR = 64 * sizeof(T) / 16;
-    const int c = tid + 256 * i;
-    return (unsigned)((c / CPR) * 64 * sizeof(T) + (c % CPR) * 16);
-  }
-  DEV void store(char* ks, char* vs, int tid) {
-#pragma unroll
-    for (int i = 0; i < CH; i++) {
-      int c = tid + 256 * i;
-      constexpr int CPR = 64 * sizeof(T) / 16;
-      int key = c / CPR, byte = (c % CPR) * 16;
-      *(uint4*)(ks + TileL<T>::krow(key, byte)) = k[i];
-      *(uint4*)(vs + TileL<T>::vrow(key, byte)) = v[i];
     }
   }
 };
@@ -171,10 +187,15 @@ __global__ void __launch_bounds__(256, 3) attn_fwd_kernel(const T* __restrict__ 
   negm[0] = negm[1] = f32x4{0, 0, 0, 0};
   lacc[0] = lacc[1] = f32x4{0, 0, 0, 0};
 
-  if constexpr (DMA) {
   const int nkt = (N + 63) / 64;
-  // the per-tile work on the staged K / V images ks, vs (both staging forms)
-  auto tile_compute = [&](int kt, const char* ks, const char* vs) {
+  // the per-tile work on the staged K / V images ks, vs -- the one body both staging forms run, so their outputs are
+  // bit-identical by construction.
+  // The lane coordinates g, li are parameters so that the register-staged bf16 instance can take them by value: it sits
+  // exactly on the 168-VGPR cap of the launch bound, and with the body reading them through references (as a plain [&]
+  // capture does) it spills 16 VGPRs (36 B/lane of scratch) around the tile loop.  The other two instances keep the
+  // references, which leaves their code as it was when the body stood in each loop.
+  typedef typename std::conditional<!DMA && !F32, int, const int&>::type lane_arg;
+  auto tile_compute = [&](int kt, const char* ks, const char* vs, lane_arg g, lane_arg li) {
     // a wave whose 32 queries are all >= N (the partial last block: N = 4096 + 5 prefix tokens) only helps stage K / V
     if (active) {
     // ---- S^T = K Q^T (- m) : acc[kb][qs], element i: key = kb*16 + 4g + i, query = qs*16 + li
@@ -294,6 +315,7 @@ __global__ void __launch_bounds__(256, 3) attn_fwd_kernel(const T* __restrict__ 
     }
     }
   };
+  if constexpr (DMA) {
     // piece p = 4 wave + i of a tile: K pieces 0..7 (waves 0, 1), V pieces 8..15 (waves 2, 3); piece p & 7 holds keys
     // 8 (p & 7) .. +7, lane l writes physical 16-B chunk l & 7 of key 8 (p & 7) + (l >> 3), i.e. the logical chunk the
     // TileL swizzle puts there (K: 16-B chunks XOR (key >> 1) & 7; V: 32-B slots XOR (key >> 1) & 3)
@@ -322,7 +344,7 @@ __global__ void __launch_bounds__(256, 3) attn_fwd_kernel(const T* __restrict__ 
     // that this tile's LDS reads cannot alias the next tile's DMA (as in the backward kernels)
     auto tile = [&](int kt, char* __restrict__ nxt, const char* __restrict__ cs) {
       if (kt + 1 < nkt) dma(kt + 1, nxt);
-      tile_compute(kt, cs, cs + L::BYTES);
+      tile_compute(kt, cs, cs + L::BYTES, g, li);
       vm_drain();           // this wave's pieces of the next tile landed ...
       __syncthreads();      // ... and every wave's; every wave done with this stage
     };
@@ -331,14 +353,10 @@ __global__ void __launch_bounds__(256, 3) attn_fwd_kernel(const T* __restrict__ 
     if (kt < nkt) tile(kt, smem1, smem);
   } else {
   Stage<T> stg;
-  const int nkt = (N + 63) / 64;
-  const auto rk = attn_rsrc(Kp, (unsigned long)N * 64 * sizeof(T)), rv = attn_rsrc(Vp, (unsigned long)N * 64 * sizeof(T));
-  unsigned vo[Stage<T>::CH];
-#pragma unroll
-  for (int i = 0; i < Stage<T>::CH; i++) vo[i] = Stage<T>::chunk_off(tid, i);
+  if constexpr (!F32) stg.init(Kp, Vp, N, tid);
   auto stage_load = [&](int key0) {
     if constexpr (F32) stg.load(Kp, Vp, key0, N, tid);
-    else stg.load_buf(rk, rv, vo, key0);
+    else stg.load(key0);
   };
   stage_load(0);
   stg.store(smem, smem + L::BYTES, tid);
@@ -348,125 +366,7 @@ __global__ void __launch_bounds__(256, 3) attn_fwd_kernel(const T* __restrict__ 
     const bool more = kt + 1 < nkt;
     if (more) stage_load((kt + 1) * 64);
     const char* ks = smem + cur * 2 * L::BYTES;
-    const char* vs = ks + L::BYTES;
-    // a wave whose 32 queries are all >= N (the partial last block: N = 4096 + 5 prefix tokens) only helps stage K / V
-    if (active) {
-    // ---- S^T = K Q^T (- m) : acc[kb][qs], element i: key = kb*16 + 4g + i, query = qs*16 + li
-    f32x4 s[4][2];
-#pragma unroll
-    for (int kb = 0; kb < 4; kb++) {
-      if constexpr (F32) {
-        s[kb][0] = f32x4{0, 0, 0, 0}; s[kb][1] = f32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int kk = 0; kk < QK; kk++) {
-          float a = *(const float*)(ks + L::krow(kb * 16 + li, (kk * 4 + g) * 4));
-          s[kb][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, qf[0][kk], s[kb][0], 0, 0, 0);
-          s[kb][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, qf[1][kk], s[kb][1], 0, 0, 0);
-        }
-      } else {
-        bf16x8 a0 = *(const bf16x8*)(ks + L::krow(kb * 16 + li, g * 16));
-        bf16x8 a1 = *(const bf16x8*)(ks + L::krow(kb * 16 + li, 64 + g * 16));
-        s[kb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[0][0], negm[0], 0, 0, 0);
-        s[kb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[1][0], negm[1], 0, 0, 0);
-        s[kb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[0][1], s[kb][0], 0, 0, 0);
-        s[kb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[1][1], s[kb][1], 0, 0, 0);
-      }
-    }
-    // ---- mask keys >= N (last tile only)
-    if (kt * 64 + 64 > N) {
-#pragma unroll
-      for (int kb = 0; kb < 4; kb++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          int key = kt * 64 + kb * 16 + 4 * g + i;
-          if (key >= N) { s[kb][0][i] = -INFINITY; s[kb][1][i] = -INFINITY; }
-        }
-    }
-    if constexpr (F32) {
-      // ---- exact online softmax per query column
-#pragma unroll
-      for (int qs = 0; qs < 2; qs++) {
-        f32x4 col[4] = {s[0][qs], s[1][qs], s[2][qs], s[3][qs]};
-        float mx = xmax4(max16(col));
-        float mnew = fmaxf(mrow[qs], mx);
-        float alpha = fexp2(mrow[qs] - mnew);
-        float sum = 0.f;
-#pragma unroll
-        for (int kb = 0; kb < 4; kb++)
-#pragma unroll
-          for (int i = 0; i < 4; i++) { float p = fexp2(s[kb][qs][i] - mnew); s[kb][qs][i] = p; sum += p; }
-        lrow[qs] = lrow[qs] * alpha + xsum4(sum);
-        mrow[qs] = mnew;
-#pragma unroll
-        for (int ds = 0; ds < 4; ds++) o[ds][qs] *= alpha;
-      }
-#pragma unroll
-      for (int kb = 0; kb < 4; kb++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          int key = kb * 16 + 4 * g + i;
-#pragma unroll
-          for (int ds = 0; ds < 4; ds++) {
-            float a = *(const float*)(vs + L::vrow(key, (ds * 16 + li) * 4));
-            o[ds][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, s[kb][0][i], o[ds][0], 0, 0, 0);
-            o[ds][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, s[kb][1][i], o[ds][1], 0, 0, 0);
-          }
-        }
-    } else {
-      // ---- lazy max: s already holds score - m.  The first tile sets m exactly; later tiles only
-      // rescale when a score exceeds m by more than RESCALE_TH (wave-uniform branch).
-      float lm0 = 0.f, lm1 = 0.f;
-      if (!FAST || kt == 0) {
-        f32x4 c0[4] = {s[0][0], s[1][0], s[2][0], s[3][0]}, c1[4] = {s[0][1], s[1][1], s[2][1], s[3][1]};
-        lm0 = max16(c0); lm1 = max16(c1);
-      }
-      if (kt == 0 || (!FAST && __any(fmaxf(lm0, lm1) > RESCALE_TH))) {
-        float lmq[2] = {lm0, lm1};
-#pragma unroll
-        for (int qs = 0; qs < 2; qs++) {
-          float d = xmax4(lmq[qs]);
-          d = kt == 0 ? d : fmaxf(d, 0.f);
-          mrow[qs] = kt == 0 ? d : mrow[qs] + d;
-          float alpha = kt == 0 ? 1.f : fexp2(-d);
-#pragma unroll
-          for (int kb = 0; kb < 4; kb++) s[kb][qs] -= d;
-#pragma unroll
-          for (int ds = 0; ds < 4; ds++) o[ds][qs] *= alpha;
-          lacc[qs] *= alpha;
-          negm[qs] = f32x4{-mrow[qs], -mrow[qs], -mrow[qs], -mrow[qs]};
-        }
-      }
-      // ---- P = exp2(s); O^T += V^T P^T ; l += 1^T P^T
-      typedef __attribute__((address_space(3))) s16x4 lds_s4;
-      bf16x8 ones;
-#pragma unroll
-      for (int e = 0; e < 8; e++) ones[e] = (bf16)1.f;
-#pragma unroll
-      for (int kst = 0; kst < 2; kst++) {
-        bf16x8 pb[2];
-#pragma unroll
-        for (int qs = 0; qs < 2; qs++)
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            pb[qs][i] = (bf16)fexp2(s[2 * kst][qs][i]);
-            pb[qs][4 + i] = (bf16)fexp2(s[2 * kst + 1][qs][i]);
-          }
-        const int q = li >> 2, p = li & 3;
-#pragma unroll
-        for (int ds = 0; ds < 4; ds++) {
-          int byte = (ds * 16 + 4 * p) * 2;
-          s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vs + L::vrow(32 * kst + 4 * g + q, byte)));
-          s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(vs + L::vrow(32 * kst + 16 + 4 * g + q, byte)));
-          bf16x4 a0 = __builtin_bit_cast(bf16x4, lo), a1 = __builtin_bit_cast(bf16x4, hi);
-          bf16x8 a = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
-          o[ds][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[0], o[ds][0], 0, 0, 0);
-          o[ds][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pb[1], o[ds][1], 0, 0, 0);
-        }
-        lacc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[0], lacc[0], 0, 0, 0);
-        lacc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[1], lacc[1], 0, 0, 0);
-      }
-    }
-    }
+    tile_compute(kt, ks, ks + L::BYTES, g, li);
     if (more) stg.store(smem + (cur ^ 1) * 2 * L::BYTES, smem + (cur ^ 1) * 2 * L::BYTES + L::BYTES, tid);
     __syncthreads();
     cur ^= 1;
@@ -540,32 +440,22 @@ __global__ void attn_delta_kernel(const T* __restrict__ O, const T* __restrict__
 }
 
 namespace {
-// 64-row x 64-d tile image used for both row reads (ds_read_b128 / scalar) and transposed reads
-template <typename T> struct Img;
-template <> struct Img<bf16> {
-  // 16-B slot XOR f((row >> 1) & 7) with f = (0,2,4,6,5,7,1,3): conflict-free for BOTH the
-  // row-fragment ds_read_b128 and the transposed ds_read_b64_tr_b16 patterns (exhaustive search
-  // over the 8! slot permutations against the gfx950 lane groups; the plain (row>>1)&7 XOR left
-  // the transposed reads 2-way conflicted)
-  static constexpr int BYTES = 64 * 128;
-  DEV static int swz(int row) { return (0x31756420u >> (((row >> 1) & 7) * 4)) & 7; }
-  DEV static int at(int row, int byte) { return row * 128 + ((((byte >> 4) ^ swz(row)) << 4) | (byte & 15)); }
-};
-template <> struct Img<float> {
+// f32 (strict parity) backward on v_mfma_f32_16x16x4_f32; the bf16 backward is the 32x32x16 pair further down.
+// 64-row x 64-d f32 tile image: 256-B rows + 16-B pad, read by scalars along rows and along columns
+struct ImgF {
   static constexpr int BYTES = 64 * 272;
   DEV static int at(int row, int byte) { return row * 272 + byte; }
 };
 
-// stage a [64 rows][64] tile of a strided tensor (row stride ld elements) into registers / LDS
-template <typename T> struct RowTile {
-  static constexpr int CH = 64 * 64 * sizeof(T) / 16 / 256;
+// stage a [64 rows][64] f32 tile of a strided tensor (row stride ld elements) into registers / LDS
+struct RowTile {
+  static constexpr int CH = 64 * 64 * 4 / 16 / 256;
   uint4 r[CH];
-  DEV void load(const T* base, long ld, int row0, int N, int tid) {
+  DEV void load(const float* base, long ld, int row0, int N, int tid) {
 #pragma unroll
     for (int i = 0; i < CH; i++) {
       int c = tid + 256 * i;
-      constexpr int CPR = 64 * sizeof(T) / 16;
-      int row = row0 + c / CPR, col = (c % CPR) * (16 / sizeof(T));
+      int row = row0 + c / 16, col = (c % 16) * 4;
       r[i] = row < N ? *(const uint4*)(base + (long)row * ld + col) : make_uint4(0, 0, 0, 0);
     }
   }
@@ -573,33 +463,13 @@ template <typename T> struct RowTile {
 #pragma unroll
     for (int i = 0; i < CH; i++) {
       int c = tid + 256 * i;
-      constexpr int CPR = 64 * sizeof(T) / 16;
-      *(uint4*)(lds + Img<T>::at(c / CPR, (c % CPR) * 16)) = r[i];
+      *(uint4*)(lds + ImgF::at(c / 16, (c % 16) * 16)) = r[i];
     }
   }
 };
 
-typedef __attribute__((address_space(3))) s16x4 lds_s4;
-// bf16 A/B fragment of a 16x32 block read TRANSPOSED from an Img<bf16>:
-// lane (g, i) gets X[row(g,j)][col0 + i] for j = 0..7 with row(g,j) = r0 + 4g + j (j<4), r0 + 16 + 4g + j-4 (j>=4)
-DEV bf16x8 tr_frag(const char* img, int r0, int col0, int lane) {
-  int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
-  int byte = (col0 + 4 * p) * 2;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(img + Img<bf16>::at(r0 + 4 * g + q, byte)));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(img + Img<bf16>::at(r0 + 16 + 4 * g + q, byte)));
-  bf16x4 a = __builtin_bit_cast(bf16x4, lo), b = __builtin_bit_cast(bf16x4, hi);
-  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-// row fragment: lane (g, i) gets X[r0 + i][kk*32 + 8g .. +7]
-DEV bf16x8 row_frag(const char* img, int r0, int kk, int lane) {
-  return *(const bf16x8*)(img + Img<bf16>::at(r0 + (lane & 15), kk * 64 + (lane >> 4) * 16));
-}
-DEV bf16x8 pack8(f32x4 a, f32x4 b) {
-  return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
-}
-DEV f32x4 mma_bf(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 DEV f32x4 mma_f(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-DEV float ldsf(const char* img, int row, int col) { return *(const float*)(img + Img<float>::at(row, col * 4)); }
+DEV float ldsf(const char* img, int row, int col) { return *(const float*)(img + ImgF::at(row, col * 4)); }
 }  // namespace
 
 // Fused backward epilogue (s3od_attn_bwd_qkv): instead of dQ / dK / dV in [B*H, N, 64], write the
@@ -612,7 +482,7 @@ DEV float ldsf(const char* img, int row, int col) { return *(const float*)(img +
 struct QkvSink {
   void* dqkv; const float* cs; const float* sn; float* ws; int P;
 };
-template <typename T>
+// f32 kernels: one token row (lane's row, d = ds*16 + 4g + i)
 DEV void qkv_sink_row(const QkvSink& o, int which, int b, int h, int H, int tok, int N, int g, const f32x4 (&val)[4], float scale,
                       f32x4 (&csum)[4]) {
   float out[4][4];
@@ -636,12 +506,10 @@ DEV void qkv_sink_row(const QkvSink& o, int which, int b, int h, int H, int tok,
 #pragma unroll
       for (int i = 0; i < 4; i++) out[ds][i] = val[ds][i] * scale;
   }
-  T* row = (T*)o.dqkv + ((long)b * N + tok) * (3L * H * 64) + (long)which * H * 64 + h * 64;
+  float* row = (float*)o.dqkv + ((long)b * N + tok) * (3L * H * 64) + (long)which * H * 64 + h * 64;
 #pragma unroll
   for (int ds = 0; ds < 4; ds++) {
-    T* dst = row + ds * 16 + 4 * g;
-    if constexpr (std::is_same<T, float>::value) *(float4*)dst = make_float4(out[ds][0], out[ds][1], out[ds][2], out[ds][3]);
-    else *(bf16x4*)dst = bf16x4{(bf16)out[ds][0], (bf16)out[ds][1], (bf16)out[ds][2], (bf16)out[ds][3]};
+    *(float4*)(row + ds * 16 + 4 * g) = make_float4(out[ds][0], out[ds][1], out[ds][2], out[ds][3]);
 #pragma unroll
     for (int i = 0; i < 4; i++) csum[ds][i] += out[ds][i];
   }
@@ -666,46 +534,39 @@ DEV void qkv_sink_colsum(const QkvSink& o, int which, int h, int H, int rep, int
   }
 }
 
-// dK, dV.  Workgroup = 4 waves x 16*KS keys of one (b,h); loop over 64-query tiles.
+// dK, dV.  Workgroup = 4 waves x 32 keys of one (b,h); loop over 64-query tiles.
 //   S  = Q K^T     (A = Q rows from LDS, B = K fragments in registers)   -> lane = key, regs = q
 //   dP = dO V^T    (A = dO rows from LDS, B = V fragments in registers)
-//   dV^T += dO^T P (A = dO^T via transposed LDS reads, B = P from the accumulators)
-//   dK^T += Q^T dS (A = Q^T via transposed LDS reads, B = dS from the accumulators)
-template <typename T, int KS>
-__global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V,
-                                                             const T* __restrict__ dO, const float* __restrict__ LSE,
-                                                             const float* __restrict__ Dl, T* __restrict__ dK, T* __restrict__ dV,
-                                                             int N, int H, QkvSink sink) {
-  constexpr bool F32 = std::is_same<T, float>::value;
-  typedef Img<T> I;
+//   dV^T += dO^T P (A = dO^T by column reads of the dO image, B = P from the accumulators)
+//   dK^T += Q^T dS (A = Q^T by column reads of the Q image, B = dS from the accumulators)
+__global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                             const float* __restrict__ V, const float* __restrict__ dO,
+                                                             const float* __restrict__ LSE, const float* __restrict__ Dl,
+                                                             float* __restrict__ dK, float* __restrict__ dV, int N, int H,
+                                                             QkvSink sink) {
+  typedef ImgF I;
+  constexpr int KS = 2;      // 16-key blocks per wave
   __shared__ __attribute__((aligned(16))) char smem[2 * (2 * I::BYTES + 512)];
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-  const T* Qp = Q + (long)bh * N * 64;
-  const T* Kp = K + (long)bh * N * 64;
-  const T* Vp = V + (long)bh * N * 64;
-  const T* dOp = dO + (long)b * N * (H * 64) + h * 64;
+  const float* Qp = Q + (long)bh * N * 64;
+  const float* Kp = K + (long)bh * N * 64;
+  const float* Vp = V + (long)bh * N * 64;
+  const float* dOp = dO + (long)b * N * (H * 64) + h * 64;
   const long ldo = (long)H * 64;
   const float* Lp = LSE + (long)bh * N;
   const float* Dp = Dl + (long)bh * N;
   const int k0 = blockIdx.x * (64 * KS) + wave * (16 * KS);
 
-  constexpr int KK = F32 ? 16 : 2;
-  typedef typename std::conditional<F32, float, bf16x8>::type frag;
-  frag kf[KS][KK], vf[KS][KK];
+  constexpr int KK = 16;     // k-steps over d=64
+  float kf[KS][KK], vf[KS][KK];
 #pragma unroll
   for (int ks = 0; ks < KS; ks++) {
     int key = k0 + ks * 16 + li;
 #pragma unroll
     for (int kk = 0; kk < KK; kk++) {
-      if constexpr (F32) {
-        kf[ks][kk] = key < N ? Kp[(long)key * 64 + kk * 4 + g] : 0.f;
-        vf[ks][kk] = key < N ? Vp[(long)key * 64 + kk * 4 + g] : 0.f;
-      } else {
-        bf16x8 z; for (int e = 0; e < 8; e++) z[e] = (bf16)0.f;
-        kf[ks][kk] = key < N ? *(const bf16x8*)(Kp + (long)key * 64 + kk * 32 + 8 * g) : z;
-        vf[ks][kk] = key < N ? *(const bf16x8*)(Vp + (long)key * 64 + kk * 32 + 8 * g) : z;
-      }
+      kf[ks][kk] = key < N ? Kp[(long)key * 64 + kk * 4 + g] : 0.f;
+      vf[ks][kk] = key < N ? Vp[(long)key * 64 + kk * 4 + g] : 0.f;
     }
   }
   f32x4 dk[4][KS], dv[4][KS];
@@ -714,7 +575,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
 #pragma unroll
     for (int j = 0; j < KS; j++) { dk[i][j] = f32x4{0, 0, 0, 0}; dv[i][j] = f32x4{0, 0, 0, 0}; }
 
-  RowTile<T> tq, tdo;
+  RowTile tq, tdo;
   float lse_r = 0.f, dl_r = 0.f;
   const int nqt = (N + 63) / 64;
   auto stage_load = [&](int qt) {
@@ -738,39 +599,28 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
     const char* dos = qs_ + I::BYTES;
     const float* lsel = (const float*)(qs_ + 2 * I::BYTES);
     const float* dll = lsel + 64;
-    // bf16: accumulators start at -LSE[q] / -delta[q] (q = qb*16 + 4g + i), so after the MFMAs
-    // s = score - lse (log2 units) and dp = dO.v - delta.
-    // f32 (strict parity): they start at zero and -LSE / -delta are added afterwards -- a dot product accumulated
-    // on top of -LSE rounds every partial sum at the magnitude of LSE (16 steps), which cost P two bits (N = 1:
-    // dV = P dO came out 4 ulp off dO); from zero the score is bit-identical to the forward's
+    // The accumulators start at zero and -LSE[q] / -delta[q] (q = qb*16 + 4g + i) are added after the MFMAs, not fed
+    // in as the C operand as the bf16 kernels do: a dot product accumulated on top of -LSE rounds every partial sum
+    // at the magnitude of LSE (16 steps), which cost P two bits (N = 1: dV = P dO came out 4 ulp off dO); from zero
+    // the score is bit-identical to the forward's
     f32x4 s[4][KS], dp[4][KS];
 #pragma unroll
-    for (int qb = 0; qb < 4; qb++) {
-      f32x4 nl = f32x4{0, 0, 0, 0}, nd = f32x4{0, 0, 0, 0};
-      if constexpr (!F32) { nl = *(const f32x4*)(lsel + qb * 16 + 4 * g); nd = *(const f32x4*)(dll + qb * 16 + 4 * g); }
+    for (int qb = 0; qb < 4; qb++)
 #pragma unroll
-      for (int ks = 0; ks < KS; ks++) { s[qb][ks] = nl; dp[qb][ks] = nd; }
-    }
+      for (int ks = 0; ks < KS; ks++) { s[qb][ks] = f32x4{0, 0, 0, 0}; dp[qb][ks] = f32x4{0, 0, 0, 0}; }
 #pragma unroll
     for (int qb = 0; qb < 4; qb++) {
 #pragma unroll
       for (int kk = 0; kk < KK; kk++) {
-        if constexpr (F32) {
-          float a = ldsf(qs_, qb * 16 + li, kk * 4 + g), c = ldsf(dos, qb * 16 + li, kk * 4 + g);
+        float a = ldsf(qs_, qb * 16 + li, kk * 4 + g), c = ldsf(dos, qb * 16 + li, kk * 4 + g);
 #pragma unroll
-          for (int ks = 0; ks < KS; ks++) { s[qb][ks] = mma_f(a, kf[ks][kk], s[qb][ks]); dp[qb][ks] = mma_f(c, vf[ks][kk], dp[qb][ks]); }
-        } else {
-          bf16x8 a = row_frag(qs_, qb * 16, kk, lane), c = row_frag(dos, qb * 16, kk, lane);
-#pragma unroll
-          for (int ks = 0; ks < KS; ks++) { s[qb][ks] = mma_bf(a, kf[ks][kk], s[qb][ks]); dp[qb][ks] = mma_bf(c, vf[ks][kk], dp[qb][ks]); }
-        }
+        for (int ks = 0; ks < KS; ks++) { s[qb][ks] = mma_f(a, kf[ks][kk], s[qb][ks]); dp[qb][ks] = mma_f(c, vf[ks][kk], dp[qb][ks]); }
       }
     }
     // P = exp2(S - LSE[q]), dS = P*(dP - delta[q])   (invalid q: LSE = +inf -> P = 0)
 #pragma unroll
     for (int qb = 0; qb < 4; qb++) {
-      f32x4 nl = f32x4{0, 0, 0, 0}, nd = f32x4{0, 0, 0, 0};
-      if constexpr (F32) { nl = *(const f32x4*)(lsel + qb * 16 + 4 * g); nd = *(const f32x4*)(dll + qb * 16 + 4 * g); }
+      const f32x4 nl = *(const f32x4*)(lsel + qb * 16 + 4 * g), nd = *(const f32x4*)(dll + qb * 16 + 4 * g);
 #pragma unroll
       for (int ks = 0; ks < KS; ks++)
 #pragma unroll
@@ -781,33 +631,18 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
         }
     }
     // dV^T += dO^T P ; dK^T += Q^T dS
-    if constexpr (F32) {
 #pragma unroll
-      for (int qb = 0; qb < 4; qb++)
+    for (int qb = 0; qb < 4; qb++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          int qq = qb * 16 + 4 * g + i;
-#pragma unroll
-          for (int ds = 0; ds < 4; ds++) {
-            float ao = ldsf(dos, qq, ds * 16 + li), aq = ldsf(qs_, qq, ds * 16 + li);
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) { dv[ds][ks] = mma_f(ao, s[qb][ks][i], dv[ds][ks]); dk[ds][ks] = mma_f(aq, dp[qb][ks][i], dk[ds][ks]); }
-          }
-        }
-    } else {
-#pragma unroll
-      for (int qst = 0; qst < 2; qst++) {
-        bf16x8 pb[KS], sb[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) { pb[ks] = pack8(s[2 * qst][ks], s[2 * qst + 1][ks]); sb[ks] = pack8(dp[2 * qst][ks], dp[2 * qst + 1][ks]); }
+      for (int i = 0; i < 4; i++) {
+        int qq = qb * 16 + 4 * g + i;
 #pragma unroll
         for (int ds = 0; ds < 4; ds++) {
-          bf16x8 ao = tr_frag(dos, 32 * qst, ds * 16, lane), aq = tr_frag(qs_, 32 * qst, ds * 16, lane);
+          float ao = ldsf(dos, qq, ds * 16 + li), aq = ldsf(qs_, qq, ds * 16 + li);
 #pragma unroll
-          for (int ks = 0; ks < KS; ks++) { dv[ds][ks] = mma_bf(ao, pb[ks], dv[ds][ks]); dk[ds][ks] = mma_bf(aq, sb[ks], dk[ds][ks]); }
+          for (int ks = 0; ks < KS; ks++) { dv[ds][ks] = mma_f(ao, s[qb][ks][i], dv[ds][ks]); dk[ds][ks] = mma_f(aq, dp[qb][ks][i], dk[ds][ks]); }
         }
       }
-    }
     if (more) stage_store(smem + (cur ^ 1) * SB);
     __syncthreads();
     cur ^= 1;
@@ -821,8 +656,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
       if (key >= N) continue;
       const f32x4 kv[4] = {dk[0][ks], dk[1][ks], dk[2][ks], dk[3][ks]};
       const f32x4 vv[4] = {dv[0][ks], dv[1][ks], dv[2][ks], dv[3][ks]};
-      qkv_sink_row<T>(sink, 1, b, h, H, key, N, g, kv, LN2, csk);
-      qkv_sink_row<T>(sink, 2, b, h, H, key, N, g, vv, 1.f, csv);
+      qkv_sink_row(sink, 1, b, h, H, key, N, g, kv, LN2, csk);
+      qkv_sink_row(sink, 2, b, h, H, key, N, g, vv, 1.f, csv);
     }
     if (sink.ws) qkv_sink_colsum(sink, 2, h, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csv);
     return;
@@ -832,45 +667,38 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const T* __restrict_
   for (int ks = 0; ks < KS; ks++) {
     int key = k0 + ks * 16 + li;
     if (key >= N) continue;
-    T* dkr = dK + ((long)bh * N + key) * 64;
-    T* dvr = dV + ((long)bh * N + key) * 64;
+    float* dkr = dK + ((long)bh * N + key) * 64;
+    float* dvr = dV + ((long)bh * N + key) * 64;
 #pragma unroll
     for (int ds = 0; ds < 4; ds++) {
       int d = ds * 16 + 4 * g;
       dk[ds][ks] *= LN2;   // d(q.k*ln2)/dk with q in log2 scaling
-      if constexpr (F32) {
-        *(float4*)(dkr + d) = make_float4(dk[ds][ks][0], dk[ds][ks][1], dk[ds][ks][2], dk[ds][ks][3]);
-        *(float4*)(dvr + d) = make_float4(dv[ds][ks][0], dv[ds][ks][1], dv[ds][ks][2], dv[ds][ks][3]);
-      } else {
-        *(bf16x4*)(dkr + d) = bf16x4{(bf16)dk[ds][ks][0], (bf16)dk[ds][ks][1], (bf16)dk[ds][ks][2], (bf16)dk[ds][ks][3]};
-        *(bf16x4*)(dvr + d) = bf16x4{(bf16)dv[ds][ks][0], (bf16)dv[ds][ks][1], (bf16)dv[ds][ks][2], (bf16)dv[ds][ks][3]};
-      }
+      *(float4*)(dkr + d) = make_float4(dk[ds][ks][0], dk[ds][ks][1], dk[ds][ks][2], dk[ds][ks][3]);
+      *(float4*)(dvr + d) = make_float4(dv[ds][ks][0], dv[ds][ks][1], dv[ds][ks][2], dv[ds][ks][3]);
     }
   }
 }
 
-// dQ (w.r.t. the pre-scaled q).  Workgroup = 4 waves x 16*QS queries; loop over 64-key tiles.
+// dQ (w.r.t. the pre-scaled q).  Workgroup = 4 waves x 32 queries; loop over 64-key tiles.
 //   S^T = K Q^T, dP^T = V dO^T (B operands Q, dO in registers)  -> lane = q, regs = keys
-//   dQ^T += K^T dS^T            (A = K^T via transposed LDS reads, B = dS^T from accumulators)
-template <typename T, int QS>
-__global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ Q, const T* __restrict__ K, const T* __restrict__ V,
-                                                           const T* __restrict__ dO, const float* __restrict__ LSE,
-                                                           const float* __restrict__ Dl, T* __restrict__ dQ, int N, int H,
-                                                           QkvSink sink) {
-  constexpr bool F32 = std::is_same<T, float>::value;
-  typedef Img<T> I;
+//   dQ^T += K^T dS^T            (A = K^T by column reads of the K image, B = dS^T from accumulators)
+__global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const float* __restrict__ Q, const float* __restrict__ K,
+                                                           const float* __restrict__ V, const float* __restrict__ dO,
+                                                           const float* __restrict__ LSE, const float* __restrict__ Dl,
+                                                           float* __restrict__ dQ, int N, int H, QkvSink sink) {
+  typedef ImgF I;
+  constexpr int QS = 2;      // 16-query blocks per wave
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * I::BYTES];
   const int bh = blockIdx.y, b = bh / H, h = bh - b * H;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-  const T* Qp = Q + (long)bh * N * 64;
-  const T* Kp = K + (long)bh * N * 64;
-  const T* Vp = V + (long)bh * N * 64;
-  const T* dOp = dO + (long)b * N * (H * 64) + h * 64;
+  const float* Qp = Q + (long)bh * N * 64;
+  const float* Kp = K + (long)bh * N * 64;
+  const float* Vp = V + (long)bh * N * 64;
+  const float* dOp = dO + (long)b * N * (H * 64) + h * 64;
   const long ldo = (long)H * 64;
   const int q0 = blockIdx.x * (64 * QS) + wave * (16 * QS);
-  constexpr int KK = F32 ? 16 : 2;
-  typedef typename std::conditional<F32, float, bf16x8>::type frag;
-  frag qf[QS][KK], of[QS][KK];
+  constexpr int KK = 16;     // k-steps over d=64
+  float qf[QS][KK], of[QS][KK];
   float Lq[QS], Dq[QS];
 #pragma unroll
   for (int qs = 0; qs < QS; qs++) {
@@ -879,14 +707,8 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
     Dq[qs] = q < N ? Dl[(long)bh * N + q] : 0.f;
 #pragma unroll
     for (int kk = 0; kk < KK; kk++) {
-      if constexpr (F32) {
-        qf[qs][kk] = q < N ? Qp[(long)q * 64 + kk * 4 + g] : 0.f;
-        of[qs][kk] = q < N ? dOp[(long)q * ldo + kk * 4 + g] : 0.f;
-      } else {
-        bf16x8 z; for (int e = 0; e < 8; e++) z[e] = (bf16)0.f;
-        qf[qs][kk] = q < N ? *(const bf16x8*)(Qp + (long)q * 64 + kk * 32 + 8 * g) : z;
-        of[qs][kk] = q < N ? *(const bf16x8*)(dOp + (long)q * ldo + kk * 32 + 8 * g) : z;
-      }
+      qf[qs][kk] = q < N ? Qp[(long)q * 64 + kk * 4 + g] : 0.f;
+      of[qs][kk] = q < N ? dOp[(long)q * ldo + kk * 4 + g] : 0.f;
     }
   }
   f32x4 dq[4][QS];
@@ -894,10 +716,10 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
   for (int i = 0; i < 4; i++)
 #pragma unroll
     for (int qs = 0; qs < QS; qs++) dq[i][qs] = f32x4{0, 0, 0, 0};
-  f32x4 nl[QS], nd[QS];   // C operands: -lse (log2 units), -delta of the lane's query column
+  f32x4 nl[QS], nd[QS];   // -lse (log2 units), -delta of the lane's query column
 #pragma unroll
   for (int qs = 0; qs < QS; qs++) { nl[qs] = f32x4{-Lq[qs], -Lq[qs], -Lq[qs], -Lq[qs]}; nd[qs] = f32x4{-Dq[qs], -Dq[qs], -Dq[qs], -Dq[qs]}; }
-  RowTile<T> tk, tv;
+  RowTile tk, tv;
   const int nkt = (N + 63) / 64;
   tk.load(Kp, 64, 0, N, tid); tv.load(Vp, 64, 0, N, tid);
   tk.store(smem, tid); tv.store(smem + I::BYTES, tid);
@@ -912,21 +734,15 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 #pragma unroll
     for (int kb = 0; kb < 4; kb++) {
 #pragma unroll
-      for (int qs = 0; qs < QS; qs++) {      // f32: from zero, -LSE / -delta added after the MFMAs (see the dK/dV pass)
-        s[kb][qs] = F32 ? f32x4{0, 0, 0, 0} : nl[qs];
-        dp[kb][qs] = F32 ? f32x4{0, 0, 0, 0} : nd[qs];
+      for (int qs = 0; qs < QS; qs++) {      // from zero, -LSE / -delta added after the MFMAs (see the dK/dV pass)
+        s[kb][qs] = f32x4{0, 0, 0, 0};
+        dp[kb][qs] = f32x4{0, 0, 0, 0};
       }
 #pragma unroll
       for (int kk = 0; kk < KK; kk++) {
-        if constexpr (F32) {
-          float a = ldsf(ks_, kb * 16 + li, kk * 4 + g), c = ldsf(vs_, kb * 16 + li, kk * 4 + g);
+        float a = ldsf(ks_, kb * 16 + li, kk * 4 + g), c = ldsf(vs_, kb * 16 + li, kk * 4 + g);
 #pragma unroll
-          for (int qs = 0; qs < QS; qs++) { s[kb][qs] = mma_f(a, qf[qs][kk], s[kb][qs]); dp[kb][qs] = mma_f(c, of[qs][kk], dp[kb][qs]); }
-        } else {
-          bf16x8 a = row_frag(ks_, kb * 16, kk, lane), c = row_frag(vs_, kb * 16, kk, lane);
-#pragma unroll
-          for (int qs = 0; qs < QS; qs++) { s[kb][qs] = mma_bf(a, qf[qs][kk], s[kb][qs]); dp[kb][qs] = mma_bf(c, of[qs][kk], dp[kb][qs]); }
-        }
+        for (int qs = 0; qs < QS; qs++) { s[kb][qs] = mma_f(a, qf[qs][kk], s[kb][qs]); dp[kb][qs] = mma_f(c, of[qs][kk], dp[kb][qs]); }
       }
     }
     // dS^T = exp2(s - lse) * (dp - delta)
@@ -935,10 +751,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 #pragma unroll
       for (int qs = 0; qs < QS; qs++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          if constexpr (F32) dp[kb][qs][i] = (dp[kb][qs][i] + nd[qs][i]) * fexp2(s[kb][qs][i] + nl[qs][i]);
-          else dp[kb][qs][i] *= fexp2(s[kb][qs][i]);
-        }
+        for (int i = 0; i < 4; i++) dp[kb][qs][i] = (dp[kb][qs][i] + nd[qs][i]) * fexp2(s[kb][qs][i] + nl[qs][i]);
     if (kt * 64 + 64 > N) {   // last tile: zero dS of keys >= N (exp2(-lse) may overflow)
 #pragma unroll
       for (int kb = 0; kb < 4; kb++)
@@ -949,33 +762,18 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
             for (int qs = 0; qs < QS; qs++) dp[kb][qs][i] = 0.f;
           }
     }
-    if constexpr (F32) {
 #pragma unroll
-      for (int kb = 0; kb < 4; kb++)
+    for (int kb = 0; kb < 4; kb++)
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-          int key = kb * 16 + 4 * g + i;
-#pragma unroll
-          for (int ds = 0; ds < 4; ds++) {
-            float a = ldsf(ks_, key, ds * 16 + li);
-#pragma unroll
-            for (int qs = 0; qs < QS; qs++) dq[ds][qs] = mma_f(a, dp[kb][qs][i], dq[ds][qs]);
-          }
-        }
-    } else {
-#pragma unroll
-      for (int kst = 0; kst < 2; kst++) {
-        bf16x8 sb[QS];
-#pragma unroll
-        for (int qs = 0; qs < QS; qs++) sb[qs] = pack8(dp[2 * kst][qs], dp[2 * kst + 1][qs]);
+      for (int i = 0; i < 4; i++) {
+        int key = kb * 16 + 4 * g + i;
 #pragma unroll
         for (int ds = 0; ds < 4; ds++) {
-          bf16x8 a = tr_frag(ks_, 32 * kst, ds * 16, lane);
+          float a = ldsf(ks_, key, ds * 16 + li);
 #pragma unroll
-          for (int qs = 0; qs < QS; qs++) dq[ds][qs] = mma_bf(a, sb[qs], dq[ds][qs]);
+          for (int qs = 0; qs < QS; qs++) dq[ds][qs] = mma_f(a, dp[kb][qs][i], dq[ds][qs]);
         }
       }
-    }
     if (more) { tk.store(smem + (cur ^ 1) * 2 * I::BYTES, tid); tv.store(smem + (cur ^ 1) * 2 * I::BYTES + I::BYTES, tid); }
     __syncthreads();
     cur ^= 1;
@@ -987,7 +785,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
       const int q = q0 + qs * 16 + li;
       if (q >= N) continue;
       const f32x4 qv[4] = {dq[0][qs], dq[1][qs], dq[2][qs], dq[3][qs]};
-      qkv_sink_row<T>(sink, 0, b, h, H, q, N, g, qv, 0.125f, csq);
+      qkv_sink_row(sink, 0, b, h, H, q, N, g, qv, 0.125f, csq);
     }
     if (sink.ws) qkv_sink_colsum(sink, 0, h, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csq);
     return;
@@ -996,12 +794,11 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
   for (int qs = 0; qs < QS; qs++) {
     int q = q0 + qs * 16 + li;
     if (q >= N) continue;
-    T* r = dQ + ((long)bh * N + q) * 64;
+    float* r = dQ + ((long)bh * N + q) * 64;
 #pragma unroll
     for (int ds = 0; ds < 4; ds++) {
       int d = ds * 16 + 4 * g;
-      if constexpr (F32) *(float4*)(r + d) = make_float4(dq[ds][qs][0], dq[ds][qs][1], dq[ds][qs][2], dq[ds][qs][3]);
-      else *(bf16x4*)(r + d) = bf16x4{(bf16)dq[ds][qs][0], (bf16)dq[ds][qs][1], (bf16)dq[ds][qs][2], (bf16)dq[ds][qs][3]};
+      *(float4*)(r + d) = make_float4(dq[ds][qs][0], dq[ds][qs][1], dq[ds][qs][2], dq[ds][qs][3]);
     }
   }
 }
@@ -1009,8 +806,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 // ===================================================================================== backward, bf16, 32x32x16
 // The bf16 backward on v_mfma_f32_32x32x16_bf16: an MFMA of this shape holds the SIMD's vector issue for 8 of
 // its 32 cycles (16x16x32: 8 of 16), so per multiply-add it leaves 1.5x the VALU issue room for the softmax
-// recompute (exp2, P*(dP - delta), two bf16 packs per score), which is what bounds the 16x16x32 kernels above
-// (PMC: ~2.7 VALU per MFMA, 22 % MFMA-busy).  Same algorithm and register-operand tricks:
+// recompute (exp2, P*(dP - delta), two bf16 packs per score), which is what bounded the 16x16x32 bf16 form of the
+// kernels above (PMC: ~2.7 VALU per MFMA, 22 % MFMA-busy; removed -- the 16x16 pair above is f32 only).  Same
+// algorithm as the f32 pair, with the register-operand tricks of the forward:
 //   dK/dV pass (one wave = 32 keys):  S = Q K^T, dP = dO V^T with the key on the lane (B = K / V fragments in
 //     registers, A = Q / dO rows from LDS, C = -LSE / -delta rows); P and dS are then, as they stand in the
 //     accumulators, the A operands of dV = P^T dO and dK = dS^T Q, whose B operands (dO, Q with the query on
@@ -1020,6 +818,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const T* __restrict__ 
 //     B = K by transposed reads).
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 namespace {
+typedef __attribute__((address_space(3))) s16x4 lds_s4;
 DEV f32x16 mma32(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 
 // 64-row x 64-col bf16 image, 128-B rows; 16-B chunk ch of row r at r*128 + 16*(ch ^ sw(r)) with
@@ -1451,19 +1250,19 @@ void launch_bwd(const void* q, const void* k, const void* v, const void* o, cons
   // needs > 256 registers -> one wave per SIMD: the whole backward measured 19 % (dK/dV) / 11 % (dQ) slower at N=4101
   hipLaunchKernelGGL(attn_delta_kernel<T>, dim3(cdiv((long)B * H * N * 8, 256)), dim3(256), 0, st, (const T*)o, (const T*)dout, delta, N, H, B * H);
   if constexpr (std::is_same<T, bf16>::value) {
-    // bf16: the 32x32x16 kernels, 4 waves per workgroup, tile loops unrolled by two (the 16x16x32 bf16 bodies,
+    // bf16: the 32x32x16 kernels, 4 waves per workgroup, tile loops unrolled by two (16x16x32 bf16 bodies,
     // 8-wave workgroups, s_setprio and interleaved variants were measured slower and removed: DESIGN §6)
     hipLaunchKernelGGL((attn_bwd_dkdv32_kernel<4>), dim3(cdiv(N, 128), B * H), dim3(256), 0, st,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dk, (bf16*)dv, N, H,
                        sink);
     hipLaunchKernelGGL((attn_bwd_dq32_kernel<4>), dim3(cdiv(N, 128), B * H), dim3(256), 0, st,
                        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)dout, lse, delta, (bf16*)dq, N, H, sink);
-    return;
   } else {
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<T, 2>), dim3(cdiv(N, 128), B * H), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                       (const T*)dout, lse, delta, (T*)dk, (T*)dv, N, H, sink);
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 2>), dim3(cdiv(N, 128), B * H), dim3(256), 0, st, (const T*)q, (const T*)k, (const T*)v,
-                       (const T*)dout, lse, delta, (T*)dq, N, H, sink);
+    // f32 (strict parity): the 16x16x4 kernels, the only instances of that pair
+    hipLaunchKernelGGL(attn_bwd_dkdv_kernel, dim3(cdiv(N, 128), B * H), dim3(256), 0, st, (const float*)q, (const float*)k,
+                       (const float*)v, (const float*)dout, lse, delta, (float*)dk, (float*)dv, N, H, sink);
+    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(cdiv(N, 128), B * H), dim3(256), 0, st, (const float*)q, (const float*)k,
+                       (const float*)v, (const float*)dout, lse, delta, (float*)dq, N, H, sink);
   }
 }
 }  // namespace

@@ -34,8 +34,8 @@ Measured on an MI355X, worst-row error of the kernel / of the emulation (72 case
   attn_fwd_kernel<float>                 o   9.8e-07 / 9.6e-07    lse 3.1e-06 / 2.1e-06
   attn_fwd_kernel<bf16, DMA>             o   3.6e-03 / 3.6e-03    lse 1.6e-03 / 1.6e-03
   attn_fwd_kernel<bf16, DMA>, FAST=0     o   3.4e-03 / 3.4e-03    lse 1.8e-03 / 2.5e-03
-  attn_bwd_dq_kernel<float, 2>           dq  6.7e-06 / 1.8e-06    (a planted row: dP - delta cancels, the kernel adds 322 keys in one chain)
-  attn_bwd_dkdv_kernel<float, 2>         dk  1.0e-06 / 1.2e-06    dv  1.1e-06 / 1.1e-06
+  attn_bwd_dq_kernel (f32)               dq  6.7e-06 / 1.8e-06    (a planted row: dP - delta cancels, the kernel adds 322 keys in one chain)
+  attn_bwd_dkdv_kernel (f32)             dk  1.0e-06 / 1.2e-06    dv  1.1e-06 / 1.1e-06
   attn_bwd_dq32_kernel (bf16)            dq  1.6e-02 / 1.6e-02
   attn_bwd_dkdv32_kernel (bf16)          dk  4.1e-03 / 4.1e-03    dv  3.7e-03 / 3.7e-03
 (N, P) = (261, 256), thirds of d_qkv and the bias sums:
@@ -439,3 +439,22 @@ def test_attention_bwd_after_overflow_fallback(dt):
         e = eg[name].view(B * H, N)[:, row]
         print(f"[{dt} overflow] planted row {row} of {name}: {float(e.max()):.3e} (allowed {tol[name]:.3e})")
         assert float(e.max()) <= tol[name], f"{name} planted row {row}: {e.tolist()} > {tol[name]:.3e}"
+
+
+# ================================================================================================ 6: the two staging forms
+@pytest.mark.parametrize("fast", ["1", "0"])
+@pytest.mark.parametrize("N", [1, 63, 65, 129, 322])
+def test_attention_fwd_bf16_staging_forms_bit_identical(N, fast, monkeypatch):
+    """S3OD_ATTN_DMA=0 (K / V staged through registers) against =1 (LDS-DMA), fixed-max and lazy-rescale loops: both
+    kernels run the one tile body of attn_fwd_kernel on the same LDS images, so o and lse are bit-identical -- an
+    equality, not a tolerance (the full-size test asserts it at N = 4101)"""
+    qs, k, v, _ = _inputs(N, "bf16", seed=4000 + N)
+    monkeypatch.setenv("S3OD_ATTN_FAST", fast)         # read per call: tests/conftest.py sets S3OD_AB=1
+    got = {}
+    for dma in ("1", "0"):
+        monkeypatch.setenv("S3OD_ATTN_DMA", dma)
+        got[dma] = _forward("bf16", qs, k, v, N)       # carved: slack untouched, every element written and finite
+    for name, a, b in zip(("o", "lse"), got["0"], got["1"]):
+        ndiff = int((a.contiguous().view(torch.uint8) != b.contiguous().view(torch.uint8)).sum())
+        print(f"[bf16 N={N} FAST={fast}] DMA=0 vs DMA=1 {name}: {ndiff} differing bytes")
+        assert torch.equal(a, b) and ndiff == 0, f"{name}: DMA=0 differs from DMA=1 in {ndiff} bytes"
