@@ -190,16 +190,12 @@ def test_quirk2_unpadded_input():
     assert tuple(x2.shape) == (1, 3, 1024, 1024)
 
 
-def test_features_gradient_vs_oracle():
-    """``features`` (path_1) carries grad as in the reference: loss = mask loss + <features, R> on the
-    f32-strict HIP path vs the oracle's autograd (per-parameter grad norm <= 2e-3, cosine >= 0.999)."""
+def _features_gradient_vs_oracle(x, masks):
+    """One f32-strict train step with loss = mask loss + <features, R> vs the oracle's autograd, per parameter."""
     from oracle import s3od_oracle as O
     from s3od_amd.loss import LossModule, FOCAL_IOU
     from s3od_amd.model import DPTSegmentation
     from s3od_amd.weights import synthetic_state_dict
-    from bench import synthetic_batch
-    torch.manual_seed(5)
-    x, masks = synthetic_batch(1, 224, 41, torch.device("cuda"))
     m = DPTSegmentation(compute_dtype="f32").cuda().train()
     m._rope_rescale = 1.0
     m.zero_grad(set_to_none=True)
@@ -230,6 +226,24 @@ def test_features_gradient_vs_oracle():
         worst_n = max(worst_n, (en, n)); worst_c = min(worst_c, (c, n))
     assert worst_n[0] <= 2e-3, worst_n
     assert worst_c[0] >= 0.999, worst_c
+
+
+def test_features_gradient_vs_oracle():
+    """``features`` (path_1) carries grad as in the reference: loss = mask loss + <features, R> on the
+    f32-strict HIP path vs the oracle's autograd (per-parameter grad norm <= 2e-3, cosine >= 0.999)."""
+    from bench import synthetic_batch
+    torch.manual_seed(5)
+    x, masks = synthetic_batch(1, 224, 41, torch.device("cuda"))
+    _features_gradient_vs_oracle(x, masks)
+
+
+def test_nonsquare_gradient_vs_oracle():
+    """The same step and criterion at B = 2 on a non-square 128 x 160 image (8 x 10 patches): every decoder grid has
+    H != W, so a backward call that swaps a layer's H and W (or states another layer's grid) cannot pass."""
+    from bench import synthetic_batch
+    torch.manual_seed(5)
+    x, masks = synthetic_batch(2, 160, 43, torch.device("cuda"))
+    _features_gradient_vs_oracle(x[:, :, :128].contiguous(), masks[:, :128].contiguous())
 
 
 def test_failed_call_drops_zero_workspaces():
