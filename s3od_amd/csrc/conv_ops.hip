@@ -1,6 +1,7 @@
 // C-ABI conv entry points: forward, data and weight gradients and the fused mask heads, routed to the
 // implicit-GEMM engine (gemm.hpp) or to the hand-pipelined kernels of gemm_ops.hip / wgrad_dma.hip.
 #include "gemm_dispatch.hpp"
+#include "conv_kernels.hpp"
 
 // ------------------------------------------------------------------ fused mask heads
 // per pixel: h = relu(conv3x3_64->32NM(feat) + b1) ; logit_k = h[32k:32k+32] . w2[k] + b2[k]
@@ -87,7 +88,7 @@ static int conv_fwd_igemm(int dtype, ConvGeo g, int M, int N, int K, int Cin, in
           Conv3A<128, decltype(rl)::value> la{};
           la.x = (const bf16*)x; la.B = g.B; la.H = g.SH; la.W = g.SW; la.SC = g.SC; la.M = M;
           la.lgc = __builtin_ctz((unsigned)(g.SC / 64));
-          DenseKC<bf16, 128> lb{(const bf16*)wp, (long)K, N, K, 0};
+          DenseKC<bf16, 128> lb{{}, (const bf16*)wp, (long)K, N, K};
           EpiStd<bf16, bf16> e{(bf16*)out, (long)Cout, 0, bias, scale, shift, (const bf16*)res1, (long)Cout, (const bf16*)res2,
                                (long)Cout, (bf16*)pre, (long)Cout, stats, act, M, N, dense_rm(), colsum};
           return launch_igemm<bf16, 256, 256, decltype(la), decltype(lb), decltype(e)>(la, lb, e, M, N, KTILES, 1, 1, st);
@@ -105,8 +106,8 @@ static int conv_fwd_igemm(int dtype, ConvGeo g, int M, int N, int K, int Cin, in
         constexpr int BN = decltype(bn)::value < CC::BN ? decltype(bn)::value : CC::BN;
         constexpr int LN = CC::PP ? CC::LN : BN;
         CC C{};
-        ConvFwdA<T, CC::LM, decltype(rl)::value, CC::W> la{}; la.x = (const T*)x; la.g = g; la.M = M; la.relu = relu_in;
-        DenseKC<T, LN, CC::W> lb{(const T*)wp, (long)K, N, K, 0};
+        ConvFwdA<T, CC::LM, decltype(rl)::value, CC::W> la{}; la.x = (const T*)x; la.g = g; la.M = M;
+        DenseKC<T, LN, CC::W> lb{{}, (const T*)wp, (long)K, N, K};
         EpiStd<T, T> e{(T*)out, (long)Cout, 0, bias, scale, shift, (const T*)res1, (long)Cout, (const T*)res2, (long)Cout,
                        (T*)pre, (long)Cout, stats, act, M, N, dense_rm(), colsum};
         return launch_igemm<T, BM, BN, decltype(la), decltype(lb), decltype(e), NST, decltype(C)::WM>(la, lb, e, M, N, KTILES, 1, 1, st);
@@ -250,7 +251,7 @@ int s3od_conv_dgrad(int dtype, int B, int H, int W, int Cin, int OH, int OW, int
             constexpr int BN = decltype(bn)::value < CC::BN ? decltype(bn)::value : CC::BN;
             constexpr int LN = CC::PP ? CC::LN : BN;
             CC C{};
-            ConvDgradA<T, CC::LM, CC::W> la{}; la.dy = (const T*)dy; la.g = g; la.M = M;
+            ConvDgradA<T, CC::LM, CC::W> la{}; la.x = (const T*)dy; la.g = g; la.M = M;
             ConvDgradB<T, LN, CC::W> lb{}; lb.w = (const T*)wp; lb.g = g; lb.NC = Cin;
             EpiStd<T, T> e{(T*)dx, (long)Cin, 0, bias, scale, shift, (const T*)res1, (long)Cin, (const T*)res2, (long)Cin,
                            (T*)pre, (long)Cin, stats, act, M, N, rm, colsum};
@@ -306,7 +307,7 @@ int s3od_conv_wgrad(int dtype, int B, int H, int W, int Cin, int OH, int OW, int
     case WgradPath::PpSlab:
     case WgradPath::PpAtomic: {
       const int KTILES = NPIX / 64;
-      DenseMC<bf16, 128> la{(const bf16*)dy, (long)Cout, NPIX, Cout};
+      DenseMC<bf16, 128> la{{}, (const bf16*)dy, (long)Cout, NPIX, Cout};
       auto pp = [&](auto rl, auto e) -> int {
         Wgrad3B<128, decltype(rl)::value> lb{}; lb.x = (const bf16*)x; lb.B = B; lb.H = H; lb.W = W; lb.Cin = Cin;
         return launch_igemm<bf16, 256, 256, decltype(la), decltype(lb), decltype(e)>(la, lb, e, M, N, KTILES, r.split, 1, st);
@@ -329,8 +330,8 @@ int s3od_conv_wgrad(int dtype, int B, int H, int W, int Cin, int OH, int OW, int
     auto go = [&](auto bm, auto rl) -> int {
       constexpr int BM = decltype(bm)::value, BN = 128, NST = 2;
       int sp = split > 0 ? split : wgrad_split<T, BM, BN, NST>(cdiv(M, BM) * cdiv(N, BN), KTILES);
-      DenseMC<T, BM> la{(const T*)dy, (long)Cout, NPIX, Cout};
-      WgradB<T, BN, decltype(rl)::value> lb{}; lb.x = (const T*)x; lb.g = g; lb.NPIX = NPIX; lb.relu = relu_x;
+      DenseMC<T, BM> la{{}, (const T*)dy, (long)Cout, NPIX, Cout};
+      WgradB<T, BN, decltype(rl)::value> lb{}; lb.x = (const T*)x; lb.g = g;
       // taps > 1: the split-K atomics go to the workspace, else straight into dW
       const bool viaws = ws != nullptr && KH * KW > 1;
       EpiWgrad e = viaws ? EpiWgrad{ws, M, N, N, 1} : EpiWgrad{dw, M, N, Cin, KH * KW};
@@ -360,14 +361,14 @@ int s3od_mask_heads_fwd(int dtype, int B, int H, int W, int NM, const void* feat
     return mask_heads_rw_launch((const bf16*)feat, (const bf16*)w1p, b1, w2, b2, logits, (bf16*)hsave, B, H, W, st);
   DISPATCH_T(dtype, {
     constexpr int BM = 128;
-    ConvFwdA<T, BM> la{}; la.x = (const T*)feat; la.g = g; la.M = M; la.relu = 0;
+    ConvFwdA<T, BM> la{}; la.x = (const T*)feat; la.g = g; la.M = M;
     EpiHeads<T> e{logits, (T*)hsave, b1, w2, b2, M, H * W, NM};
     // 2 K stages -> 2 workgroups per CU, so one's epilogue overlaps the other's K loop
     if (NM == 3) {
-      DenseKC<T, 128> lb{(const T*)w1p, (long)K, N, K, 0};
+      DenseKC<T, 128> lb{{}, (const T*)w1p, (long)K, N, K};
       return launch_igemm<T, BM, 128, decltype(la), decltype(lb), decltype(e), 2>(la, lb, e, M, 128, cdiv(K, KT<T>::BK), 1, 1, st);
     }
-    DenseKC<T, 64> lb{(const T*)w1p, (long)K, N, K, 0};
+    DenseKC<T, 64> lb{{}, (const T*)w1p, (long)K, N, K};
     return launch_igemm<T, BM, 64, decltype(la), decltype(lb), decltype(e), 2>(la, lb, e, M, 64, cdiv(K, KT<T>::BK), 1, 1, st);
   });
   return 0;

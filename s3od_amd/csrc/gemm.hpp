@@ -8,16 +8,20 @@
 //   * conv dgrad / ConvTranspose forward       A = gather by output-parity class
 //   * conv / ConvT wgrad                       B = NHWC gather
 //
-// Tiles: BM x BN x BK with BK*sizeof(T) = 128 bytes (bf16: BK=64, f32: BK=32); 256 threads
-// = 4 waves in a 2x2 grid, each wave owning a (BM/2)x(BN/2) sub-tile of 16x16 MFMA blocks.
-//   T = bf16 : v_mfma_f32_16x16x32_bf16 (fp32 accumulate)          -- fast path
-//   T = float: v_mfma_f32_16x16x4_f32  (exact fp32 fma chains)     -- strict parity path
-// Global->LDS: register staging (16 B per lane per chunk), double-buffered LDS, one
-// barrier per K tile.  LDS images:
+// K tiles are 128 bytes deep: bf16 BK = 64 on v_mfma_f32_16x16x32_bf16 (fast path), f32 BK = 32 on
+// v_mfma_f32_16x16x4_f32 (exact fp32 fma chains, strict parity path).  Operands go global -> LDS by LDS-DMA issued by
+// the loader structs below, never through registers.  Three kernels share the loaders and the epilogue functors:
+//   igemm_kernel     512 threads = 8 waves (WM x WN, 2 per SIMD), the BM x BN tiles of gemm_dispatch.hpp, bf16 and f32;
+//                    a ring of NST = 2 or 3 LDS stages filled NST - 1 K tiles ahead, one raw barrier per K tile
+//   igemm_pp_kernel  512 threads = 8 waves as 2 (M) x 4 (N), one 256 x 256 bf16 tile; two LDS buffers of four 128-row
+//                    half images (loaders with R = 128), the two M halves of a SIMD one barrier apart (ping-pong)
+//   igemm_q_kernel   256 threads = 4 waves, one per SIMD, 128 x 128 each of a 256 x 256 bf16 tile, AGPR accumulators
+//                    (gemm_q.hip, with its k-step loaders KStep and readers QFrag); a ring of four 32-deep k-steps
+// The two LDS images of a K tile (the 4-wave kernel's k-step images are the same two, 32 k deep):
 //   KC tile [rows][128 B], 16-B slots XOR-swizzled by ((row>>1)&7)  -> ds_read_b128 conflict-free
 //   MC tile [BK][rows*sizeof(T)], 32-B slots XOR-swizzled by g(k)  -> ds_read_b64_tr_b16
-// Epilogue: accumulators are staged through LDS as an fp32 tile and handed to a
-// block-level functor (bias / BN-fold / activation / residual / RoPE / atomics ...).
+// Epilogue: the accumulators are staged through LDS as an fp32 tile and handed to a block-level functor (bias /
+// BN-fold / activation / residual / RoPE / atomics ...).
 #pragma once
 #include "common.hpp"
 #include <algorithm>
@@ -28,11 +32,10 @@ template <typename T> struct KT { static constexpr int BK = 64; };
 template <> struct KT<float> { static constexpr int BK = 32; };
 
 DEV int kc_off(int r, int byte) { return r * 128 + ((((byte >> 4) ^ ((r >> 1) & 7)) << 4) | (byte & 15)); }
-template <int RB> DEV int mc_off(int k, int byte) {
-  constexpr int SLOTS = RB / 32;
-  int g = ((k & 3) | (((k >> 3) & 1) << 2)) & (SLOTS - 1);
-  return k * RB + ((((byte >> 5) ^ g) << 5) | (byte & 31));
-}
+// MC image, rows of RB bytes: the logical 32-B slot s of k-row k sits at physical slot s ^ g(k)
+template <int RB> DEV int mc_g(int k) { return ((k & 3) | (((k >> 3) & 1) << 2)) & (RB / 32 - 1); }
+template <int RB> DEV int mc_logical_byte(int k, int phys) { return (((phys >> 5) ^ mc_g<RB>(k)) << 5) | (phys & 31); }
+template <int RB> DEV int mc_off(int k, int byte) { return k * RB + mc_logical_byte<RB>(k, byte); }
 
 // ------------------------------------------------------------------ geometry helpers
 // GEMM rows enumerate pixels (b, y', x') of a "row grid" RH x RW.  For dense/FWD tiles the
@@ -87,18 +90,16 @@ template <typename T> DEV uint4 relu16(uint4 v) {
 }
 
 // ------------------------------------------------------------------ operand loaders
-// Global -> LDS by LDS-DMA through a buffer resource (buffer_load_dwordx4 ... lds): one wave
-// instruction writes 1 KiB of LDS lane-linearly (M0 = wave base, + lane*16), so the XOR
-// swizzles are applied to the per-lane SOURCE offset (guide §5.4 rule 21).
+// buffer_load_dwordx4 ... lds through a buffer resource: one wave instruction writes 1 KiB of LDS lane-linearly
+// (M0 = wave base, + lane*16), so the XOR swizzles are applied to the per-lane SOURCE offset (guide §5.4 rule 21).
 //   * the descriptor (base, byte size) is built from kernel arguments only -> SGPRs;
-//   * each lane keeps a 32-bit byte offset that is advanced by a uniform step per K tile, so the
-//     steady-state address cost is ~1 VALU per load (no 64-bit pointer math);
-//   * out-of-range chunks (padding taps, row/column tails) use an offset beyond the descriptor's
-//     size: the hardware range check returns zeros (no zero page, no per-load select);
+//   * each lane keeps a 32-bit byte offset advanced by a uniform step per K tile: ~1 VALU per load, no 64-bit math;
+//   * out-of-range chunks (padding taps, row / column tails) use an offset beyond the descriptor's size: the hardware
+//     range check returns zeros (no zero page, no per-load select);
 //   * the wave index is readfirstlane'd so every M0 value is computed on the scalar unit.
-// A tile of R rows is R*128 bytes: NIW = R*128/1024/GEMM_WAVES = R/64 instructions per wave.
-//   KC image: instruction slot o = (wave*NIW + i)*1024 + lane*16 -> row o>>7, physical 16-B slot
-//             (o>>4)&7, logical chunk = phys ^ ((row>>1)&7)
+// A tile of R rows is R*128 bytes, i.e. NIW = R/8/NW instructions per wave.  Instruction slot o = (wave*NIW + i)*1024 +
+// lane*16:
+//   KC image: row o>>7, physical 16-B slot (o>>4)&7, logical chunk = phys ^ ((row>>1)&7)
 //   MC image: k-row o / RB, physical byte o % RB, logical 32-B slot = phys32 ^ g(k)
 // Operands must be < 3.75 GiB (checked on the host by buf_ok()).
 constexpr unsigned long BUF_MAX = 0xF0000000ul;
@@ -113,57 +114,30 @@ DEV void blds16(__amdgpu_buffer_rsrc_t r, unsigned voff, char* lds_wave_base) {
 }
 DEV int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
-// Where a loader's 16-B-per-lane chunk i goes: every loader computes one buffer offset per chunk (source-side
-// swizzle, OOB -> zeros) and hands it to the sink, which LDS-DMAs it straight into the lane-linear LDS image
-// (buffer_load_dwordx4 ... lds).
-struct DmaSink {
-  char* base;                                    // tile + wave * NIW * 1024
-  DEV void operator()(int i, __amdgpu_buffer_rsrc_t r, unsigned voff) const { blds16(r, voff, base + i * 1024); }
-};
 #define HD __host__ __device__
 
-// 8 x 32-pixel output tiles of the 3x3 halo weight-gradient kernels (gemm_ops.hip, wgrad_dma.hip)
-constexpr int HT_TH = 8, HT_TW = 32, HT_HR = HT_TH + 2, HT_HC = HT_TW + 2, HT_PX = HT_HR * HT_HC;
-// LDS-DMA 3x3 weight gradient, 64 x 64 channel blocks (wgrad_dma.hip; needs H % 8 == 0, W % 32 == 0)
-int wgrad3x3_dma_launch(bool relu_x, const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT,
-                        hipStream_t st);
-// The hand-pipelined bf16 conv kernels of gemm_ops.hip (the entries of conv_ops.hip check the shapes they take).
-// Register-weight 3x3 s1 p1 convs over 64 input channels: forward 64 -> 64 (+ ReLU), the ReLU'-masked data gradient
-// (Cout 64 or 96 channels of dy, + column sums) and the three fused mask heads; rw_ok = dtype, size limits, knob
-bool rw_ok(int dtype, int B, int H, int W);
-int conv3x3_rw_launch(bool relu, const bf16* x, const bf16* w, const float* bias, bf16* out, int B, int H, int W,
-                      hipStream_t st);
-int conv3x3_rw_dgrad_launch(int Cout, const bf16* dy, const bf16* wT, const bf16* res1, float* colsum, bf16* dx, int B,
-                            int H, int W, hipStream_t st);
-int mask_heads_rw_launch(const bf16* feat, const bf16* w1p, const float* b1, const float* w2, const float* b2,
-                         float* logits, bf16* hsave, int B, int H, int W, hipStream_t st);
-// ConvTranspose2d(128, 64, 4, 2, 1) forward and its data gradient, the strided Conv2d(64, 128, 4, 2, 1); H x W = the
-// 128-channel grid
-bool convt_rw_ok(int dtype, int B, int H, int W);
-int convT4s2_rw_launch(const bf16* x, const bf16* wt, const float* bias, bool relu, bf16* out, int B, int H, int W,
-                       hipStream_t st);
-int conv4s2_rw_launch(const bf16* x, const bf16* w, float* colsum, bf16* out, int B, int H, int W, hipStream_t st);
-// weight gradients into the zeroed GEMM-layout workspace ws: register-staged 3x3 halo tiles (CoT % 64 == 0 or 96) and
-// the 4x4 s2 conv view by LDS-DMA (CinT, CoT multiples of 64)
-int wgrad3x3_halo_launch(bool relu_x, const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT,
-                         hipStream_t st);
-int wgrad4s2_dma_launch(const bf16* dy, const bf16* x, float* ws, int B, int OH, int OW, int CinT, int CoT, hipStream_t st);
-
-template <int RB> DEV int mc_logical_byte(int k, int phys) {
-  constexpr int SLOTS = RB / 32;
-  int g = ((k & 3) | (((k >> 3) & 1) << 2)) & (SLOTS - 1);
-  return (((phys >> 5) ^ g) << 5) | (phys & 31);
-}
-
-template <typename T, int R, int NW = GEMM_WAVES> struct KCGeom {
-  static constexpr int NIW = R * 128 / 1024 / NW, EPC = 16 / sizeof(T), BK = KT<T>::BK;
+// What the loaders of an R-row tile image on NW waves share, as their empty base G = KCGeom or MCGeom: ROWS, NIW and
+// the LDS destination of a DMA instruction (TileGeom); KCL, RELU (= ReLU on the fragments read from this operand's
+// image), BK and the image's lane -> chunk map (KCGeom / MCGeom).  A loader adds its arguments, its per-lane state,
+// setup() and issue(kt, tile); an initialiser list of a loader starts with the base's {}.
+template <int R, int NW> struct TileGeom {
+  static constexpr int ROWS = R, NIW = R * 128 / 1024 / NW;
   static_assert(NIW >= 1, "tile too small for the wave count");
+  // where this wave's DMA instructions of a tile image land: instruction i at dst(tile) + i * 1024
+  DEV static char* dst(char* tile) { return tile + wave_id() * NIW * 1024; }
+};
+template <typename T, int R, int NW = GEMM_WAVES, bool RELU_ = false> struct KCGeom : TileGeom<R, NW> {
+  using TileGeom<R, NW>::NIW;
+  static constexpr bool KCL = true, RELU = RELU_;
+  static constexpr int EPC = 16 / sizeof(T), BK = KT<T>::BK;
   // row and logical element offset (within the k tile) of this lane's chunk of instruction i
   DEV static int row(int wave, int i, int lane) { return (wave * NIW + i) * 8 + (lane >> 3); }
   DEV static int kel(int wave, int i, int lane) { int r = row(wave, i, lane); return ((lane & 7) ^ ((r >> 1) & 7)) * EPC; }
 };
-template <typename T, int R, int NW = GEMM_WAVES> struct MCGeom {
-  static constexpr int NIW = R * 128 / 1024 / NW, RB = R * sizeof(T), BK = KT<T>::BK;
+template <typename T, int R, int NW = GEMM_WAVES, bool RELU_ = false> struct MCGeom : TileGeom<R, NW> {
+  using TileGeom<R, NW>::NIW;
+  static constexpr bool KCL = false, RELU = RELU_;
+  static constexpr int RB = R * sizeof(T), BK = KT<T>::BK;
   DEV static int krow(int wave, int i, int lane) { return ((wave * NIW + i) * 1024 + lane * 16) / RB; }
   DEV static int col(int wave, int i, int lane) {
     int o = ((wave * NIW + i) * 1024 + lane * 16) % RB;
@@ -171,74 +145,69 @@ template <typename T, int R, int NW = GEMM_WAVES> struct MCGeom {
   }
 };
 
-template <typename T, int R, int NW = GEMM_WAVES> struct DenseKC {          // X[row*ld + k]
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = true, RELU = false;
-  typedef KCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
-  const T* p; long ld; int nrows, K; int relu;
+template <typename T, int R, int NW = GEMM_WAVES> struct DenseKC : KCGeom<T, R, NW> {          // X[row*ld + k]
+  typedef KCGeom<T, R, NW> G;
+  const T* p; long ld; int nrows, K;
   const T* pb; unsigned long nb;           // this block's row window (descriptor rebased per block)
-  unsigned vo[NIW]; int kel[NIW];
+  unsigned vo[G::NIW]; int kel[G::NIW];
   // the descriptor only ever spans the R rows of one block, so the tensor itself may exceed 4 GiB
-  HD unsigned long bytes() const { return ((unsigned long)(R - 1) * ld + K) * sizeof(T); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX && (unsigned long)K * sizeof(T) < 0x4000000ul; }
+  HD bool buf_ok() const {
+    return ((unsigned long)(R - 1) * ld + K) * sizeof(T) < BUF_MAX && (unsigned long)K * sizeof(T) < 0x4000000ul;
+  }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
     const int rem = nrows - t0;
     pb = p + (long)t0 * ld;
     nb = rem > 0 ? ((unsigned long)(min(rem, R) - 1) * ld + K) * sizeof(T) : 0;
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       int r = G::row(wave, i, lane);
       kel[i] = G::kel(wave, i, lane);
       vo[i] = r < rem ? (unsigned)(((long)r * ld + kel[i]) * sizeof(T)) : BUF_OOB;
     }
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
     const auto rs = make_rsrc(pb, nb);
-    const unsigned adv = (unsigned)(kt * BK * sizeof(T));
-    if ((kt + 1) * BK > K) {          // K tail (uniform branch)
+    const unsigned adv = (unsigned)(kt * G::BK * sizeof(T));
+    if ((kt + 1) * G::BK > K) {          // K tail (uniform branch)
 #pragma unroll
-      for (int i = 0; i < NIW; i++) sk(i, rs, kt * BK + kel[i] < K ? vo[i] + adv : BUF_OOB);
+      for (int i = 0; i < G::NIW; i++) blds16(rs, kt * G::BK + kel[i] < K ? vo[i] + adv : BUF_OOB, d + i * 1024);
       return;
     }
 #pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, vo[i] + adv);
+    for (int i = 0; i < G::NIW; i++) blds16(rs, vo[i] + adv, d + i * 1024);
   }
 };
 
-template <typename T, int R, int NW = GEMM_WAVES> struct DenseMC {          // X[k*ld + col]
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = false, RELU = false;
-  typedef MCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
+template <typename T, int R, int NW = GEMM_WAVES> struct DenseMC : MCGeom<T, R, NW> {          // X[k*ld + col]
+  typedef MCGeom<T, R, NW> G;
   const T* p; long ld; int K, ncols;
-  int relu = 0;
-  unsigned vo[NIW]; int kr[NIW]; bool cv[NIW];
+  unsigned vo[G::NIW]; int kr[G::NIW]; bool cv[G::NIW];
   // the descriptor is rebased to each K tile's first row: only BK rows need to be addressable
   HD unsigned long total() const { return ((unsigned long)(K - 1) * ld + ncols) * sizeof(T); }
-  HD unsigned long bytes() const { return ((unsigned long)BK * ld) * sizeof(T); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX; }
+  HD bool buf_ok() const { return ((unsigned long)G::BK * ld) * sizeof(T) < BUF_MAX; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       kr[i] = G::krow(wave, i, lane);
       int cl = t0 + G::col(wave, i, lane);
       cv[i] = cl < ncols;
       vo[i] = (unsigned)(((long)kr[i] * ld + cl) * sizeof(T));
     }
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
-    const long e0 = (long)kt * BK * ld;
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
+    const long e0 = (long)kt * G::BK * ld;
     const auto rs = make_rsrc(p + e0, total() - (unsigned long)e0 * sizeof(T));
-    if ((kt + 1) * BK > K) {          // K tail (uniform branch)
+    if ((kt + 1) * G::BK > K) {          // K tail (uniform branch)
 #pragma unroll
-      for (int i = 0; i < NIW; i++) sk(i, rs, cv[i] && kt * BK + kr[i] < K ? vo[i] : BUF_OOB);
+      for (int i = 0; i < G::NIW; i++) blds16(rs, cv[i] && kt * G::BK + kr[i] < K ? vo[i] : BUF_OOB, d + i * 1024);
       return;
     }
 #pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, cv[i] ? vo[i] : BUF_OOB);
+    for (int i = 0; i < G::NIW; i++) blds16(rs, cv[i] ? vo[i] : BUF_OOB, d + i * 1024);
   }
 };
 
@@ -278,20 +247,23 @@ struct TapWalk {
   DEV static void tap_after(int TW, int th1, int tw1, int& th2, int& tw2) { tw2 = tw1 + 1; th2 = th1; if (tw2 == TW) { tw2 = 0; th2++; } }
 };
 
-// conv forward A operand: rows = output pixels (b,oy,ox) of RH x RW, k = tap*SC + c
-template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct ConvFwdA {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = true, RELU = RELU_;
-  typedef KCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
-  const T* x; ConvGeo g; int M; int relu;
+// conv A operand (KC image): rows = pixels of the row grid RH x RW, k = tap*SC + c, one tap = one source pixel of x:
+//   forward im2col (DGRAD = false): origin (oy*s - p, ox*s - p), source = origin + (th, tw), KH x KW taps
+//   parity-class dgrad / ConvT (DGRAD = true): origin (y' + qy0, x' + qx0), source = origin - (jh, jw), nth x ntw taps
+// (the tap step is a macro, not a function: as a plain expression it compiles to the code of the two former loaders)
+#define TAP_STEP(a, d) (DGRAD ? (a) - (d) : (a) + (d))
+template <typename T, int R, bool DGRAD, bool RELU_, int NW> struct ConvGatherA : KCGeom<T, R, NW, RELU_> {
+  typedef KCGeom<T, R, NW, RELU_> G;
+  const T* x; ConvGeo g; int M;
   const T* xb; unsigned long nb;          // image window of this block (rebased descriptor)
-  int iy0[NIW], ix0[NIW], pix0[NIW];      // top-left input pixel (may be outside) and its element offset + kel
-  int kl[NIW];
-  unsigned base[NIW];
+  int iy0[G::NIW], ix0[G::NIW], pix0[G::NIW];      // origin pixel (may be outside) and its element offset + kel
+  int kl[G::NIW];
+  unsigned base[G::NIW];
   TapWalk tw;
   HD unsigned long img_bytes() const { return (unsigned long)g.SH * g.SW * g.SC * sizeof(T); }
-  HD unsigned long bytes() const { return img_window_bytes(R, g.RH * g.RW, g.B, img_bytes()); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX && 2 * g.SC >= BK; }
+  HD bool buf_ok() const { return img_window_bytes(R, g.RH * g.RW, g.B, img_bytes()) < BUF_MAX && 2 * g.SC >= G::BK; }
+  DEV int ntaps() const { if constexpr (DGRAD) return g.nth * g.ntw; else return g.KH * g.KW; }
+  DEV int tap_w() const { if constexpr (DGRAD) return g.ntw > 0 ? g.ntw : 1; else return g.KW; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
     int hw = g.RH * g.RW;
@@ -299,67 +271,71 @@ template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Con
     xb = x + (long)b0 * g.SH * g.SW * g.SC;
     nb = (unsigned long)(b1 - b0 + 1) * img_bytes();
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       int m = t0 + G::row(wave, i, lane);
       int kel = G::kel(wave, i, lane);
       kl[i] = kel;
       if (m < M) {
-        int b = m / hw; int r = m - b * hw; int oy = r / g.RW;
-        iy0[i] = oy * g.s - g.p; ix0[i] = (r - oy * g.RW) * g.s - g.p;
+        int b = m / hw; int r = m - b * hw; int ry = r / g.RW;
+        if constexpr (DGRAD) { iy0[i] = ry + g.qy0; ix0[i] = (r - ry * g.RW) + g.qx0; }
+        else { iy0[i] = ry * g.s - g.p; ix0[i] = (r - ry * g.RW) * g.s - g.p; }
         pix0[i] = (((b - b0) * g.SH + iy0[i]) * g.SW + ix0[i]) * g.SC + kel;
-      } else { iy0[i] = -0x4000000; ix0[i] = 0; pix0[i] = 0; }
+      } else { iy0[i] = -0x4000000; ix0[i] = 0; pix0[i] = 0; }     // M tail: no tap of this row is inside the image
     }
     tw = TapWalk{};
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
     const auto rs = make_rsrc(xb, nb);
-    if (g.SC % BK) {                 // channels not a multiple of BK: per-lane tap (rare shapes)
-      tw.step_any(kt, BK, g.SC, g.KW);
-      int th1, tw1, th2, tw2; tw.next_tap(g.KW, th1, tw1); TapWalk::tap_after(g.KW, th1, tw1, th2, tw2);
+    const int TW = tap_w();
+    if (g.SC % G::BK) {              // channels not a multiple of BK: per-lane tap (rare shapes)
+      tw.step_any(kt, G::BK, g.SC, TW);
+      int th1, tw1, th2, tw2; tw.next_tap(TW, th1, tw1); TapWalk::tap_after(TW, th1, tw1, th2, tw2);
 #pragma unroll
-      for (int i = 0; i < NIW; i++) {
+      for (int i = 0; i < G::NIW; i++) {
         int c = tw.c0 + kl[i];
         const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
         int th = wr == 2 ? th2 : wr ? th1 : tw.th, tww = wr == 2 ? tw2 : wr ? tw1 : tw.tw;
-        int iy = iy0[i] + th, ix = ix0[i] + tww;
-        bool ok = tw.tap + wr < g.KH * g.KW && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
-        int off = pix0[i] - kl[i] + (th * g.SW + tww) * g.SC + (c - wr * g.SC);
-        sk(i, rs, ok ? (unsigned)off * (unsigned)sizeof(T) : BUF_OOB);
+        int iy = TAP_STEP(iy0[i], th), ix = TAP_STEP(ix0[i], tww);
+        bool ok = tw.tap + wr < ntaps() && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
+        int off = TAP_STEP(pix0[i] - kl[i], (th * g.SW + tww) * g.SC) + (c - wr * g.SC);
+        blds16(rs, ok ? (unsigned)off * (unsigned)sizeof(T) : BUF_OOB, d + i * 1024);
       }
       return;
     }
-    if (tw.step(kt, BK, g.SC, g.KW)) {
-      const bool tv = tw.tap < g.KH * g.KW;
+    if (tw.step(kt, G::BK, g.SC, TW)) {
+      const bool tv = tw.tap < ntaps();
       const int toff = (tw.th * g.SW + tw.tw) * g.SC;
 #pragma unroll
-      for (int i = 0; i < NIW; i++) {
-        int iy = iy0[i] + tw.th, ix = ix0[i] + tw.tw;
+      for (int i = 0; i < G::NIW; i++) {
+        int iy = TAP_STEP(iy0[i], tw.th), ix = TAP_STEP(ix0[i], tw.tw);
         bool ok = tv && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
-        base[i] = ok ? (unsigned)(pix0[i] + toff) * (unsigned)sizeof(T) : BUF_OOB;
+        base[i] = ok ? (unsigned)TAP_STEP(pix0[i], toff) * (unsigned)sizeof(T) : BUF_OOB;
       }
     }
     const unsigned cb = (unsigned)(tw.c0 * sizeof(T));
 #pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, base[i] + cb);
+    for (int i = 0; i < G::NIW; i++) blds16(rs, base[i] + cb, d + i * 1024);
   }
 };
+template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES>
+struct ConvFwdA : ConvGatherA<T, R, false, RELU_, NW> {};
+template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradA : ConvGatherA<T, R, true, false, NW> {};
+#undef TAP_STEP
 
 // 3x3 / stride 1 / pad 1 conv forward A operand for the 256x256 ping-pong kernel (bf16, SC a power-of-two multiple
 // of BK): rows = output pixels (b, oy, ox) of H x W, k = tap*SC + c.  Per lane and chunk only the element offset of
 // the CENTRE pixel is kept, plus a 9-bit tap-validity mask (every chunk's mask in one register), so a K tile's
 // offset is pix + a uniform (tap, channel) step and ConvFwdA's per-lane walker state (which spills beside the
 // ping-pong body's 240 live registers) is gone.
-template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Conv3A {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = true, RELU = RELU_;
-  typedef KCGeom<bf16, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
-  static_assert(NIW <= 3, "the tap masks of at most 3 chunks share one register");
+template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Conv3A : KCGeom<bf16, R, NW, RELU_> {
+  typedef KCGeom<bf16, R, NW, RELU_> G;
+  static_assert(G::NIW <= 3, "the tap masks of at most 3 chunks share one register");
   const bf16* x; int B, H, W, SC, M, lgc;   // lgc = log2(SC / BK)
   const bf16* xb; unsigned long nb;        // image window of this block (rebased descriptor)
-  int pix[NIW]; unsigned mask;
+  int pix[G::NIW]; unsigned mask;
   HD unsigned long img_bytes() const { return (unsigned long)H * W * SC * 2; }
-  HD bool buf_ok() const { return img_window_bytes(R, H * W, B, img_bytes()) < BUF_MAX && (BK << lgc) == SC; }
+  HD bool buf_ok() const { return img_window_bytes(R, H * W, B, img_bytes()) < BUF_MAX && (G::BK << lgc) == SC; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id(), hw = H * W;
     const int b0 = min(t0, M - 1) / hw, b1 = min(t0 + R - 1, M - 1) / hw;
@@ -367,7 +343,7 @@ template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Conv3A {
     nb = (unsigned long)(b1 - b0 + 1) * img_bytes();
     mask = 0;
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       const int m = t0 + G::row(wave, i, lane);
       pix[i] = 0;
       if (m < M) {
@@ -381,112 +357,43 @@ template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Conv3A {
       }
     }
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
     const auto rs = make_rsrc(xb, nb);
-    const int tap = kt >> lgc, c0 = (kt - (tap << lgc)) * BK;
+    const int tap = kt >> lgc, c0 = (kt - (tap << lgc)) * G::BK;
     const int ty = tap / 3, tx = tap - 3 * ty;
     const int toff = ((ty - 1) * W + (tx - 1)) * SC + c0;
 #pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, ((mask >> (10 * i + tap)) & 1u) ? (unsigned)(pix[i] + toff) * 2u : BUF_OOB);
+    for (int i = 0; i < G::NIW; i++)
+      blds16(rs, ((mask >> (10 * i + tap)) & 1u) ? (unsigned)(pix[i] + toff) * 2u : BUF_OOB, d + i * 1024);
   }
 };
 
-// dgrad / ConvT A operand: rows = class pixels (b, y', x'), k = (jh*ntw + jw)*SC + c
-template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradA {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = true, RELU = false;
-  typedef KCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
-  const T* dy; ConvGeo g; int M;
-  int relu = 0;
-  const T* yb; unsigned long nb;          // image window of this block (rebased descriptor)
-  int ry[NIW], rx[NIW], pix0[NIW], kl[NIW];
-  unsigned base[NIW];
-  TapWalk tw;
-  HD unsigned long img_bytes() const { return (unsigned long)g.SH * g.SW * g.SC * sizeof(T); }
-  HD unsigned long bytes() const { return img_window_bytes(R, g.RH * g.RW, g.B, img_bytes()); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX && 2 * g.SC >= BK; }
-  DEV void setup(int t0, int tid) {
-    const int lane = tid & 63, wave = wave_id();
-    int hw = g.RH * g.RW;
-    const int b0 = min(t0, M - 1) / hw, b1 = min(t0 + R - 1, M - 1) / hw;
-    yb = dy + (long)b0 * g.SH * g.SW * g.SC;
-    nb = (unsigned long)(b1 - b0 + 1) * img_bytes();
-#pragma unroll
-    for (int i = 0; i < NIW; i++) {
-      int m = t0 + G::row(wave, i, lane);
-      int kel = G::kel(wave, i, lane);
-      kl[i] = kel;
-      if (m < M) {
-        int b = m / hw; int r = m - b * hw; int yy = r / g.RW;
-        ry[i] = yy + g.qy0; rx[i] = (r - yy * g.RW) + g.qx0;
-        pix0[i] = (((b - b0) * g.SH + ry[i]) * g.SW + rx[i]) * g.SC + kel;
-      } else { ry[i] = -0x4000000; rx[i] = 0; pix0[i] = 0; }
-    }
-    tw = TapWalk{};
-  }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
-    const auto rs = make_rsrc(yb, nb);
-    const int TW = g.ntw > 0 ? g.ntw : 1;
-    if (g.SC % BK) {                 // channels not a multiple of BK: per-lane tap (rare shapes)
-      tw.step_any(kt, BK, g.SC, TW);
-      int th1, tw1, th2, tw2; tw.next_tap(TW, th1, tw1); TapWalk::tap_after(TW, th1, tw1, th2, tw2);
-#pragma unroll
-      for (int i = 0; i < NIW; i++) {
-        int c = tw.c0 + kl[i];
-        const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
-        int th = wr == 2 ? th2 : wr ? th1 : tw.th, tww = wr == 2 ? tw2 : wr ? tw1 : tw.tw;
-        int sy = ry[i] - th, sx = rx[i] - tww;
-        bool ok = tw.tap + wr < g.nth * g.ntw && (unsigned)sy < (unsigned)g.SH && (unsigned)sx < (unsigned)g.SW;
-        int off = pix0[i] - kl[i] - (th * g.SW + tww) * g.SC + (c - wr * g.SC);
-        sk(i, rs, ok ? (unsigned)off * (unsigned)sizeof(T) : BUF_OOB);
-      }
-      return;
-    }
-    if (tw.step(kt, BK, g.SC, TW)) {
-      const bool tv = tw.tap < g.nth * g.ntw;
-      const int toff = (tw.th * g.SW + tw.tw) * g.SC;
-#pragma unroll
-      for (int i = 0; i < NIW; i++) {
-        int sy = ry[i] - tw.th, sx = rx[i] - tw.tw;
-        bool ok = tv && (unsigned)sy < (unsigned)g.SH && (unsigned)sx < (unsigned)g.SW;
-        base[i] = ok ? (unsigned)(pix0[i] - toff) * (unsigned)sizeof(T) : BUF_OOB;
-      }
-    }
-    const unsigned cb = (unsigned)(tw.c0 * sizeof(T));
-#pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, base[i] + cb);
-  }
-};
 
 // dgrad / ConvT B operand (MC): B[k=(jh,jw,c)][n] = W[c][kh0+s*jh][kw0+s*jw][n], W repacked [C][KH][KW][N]
-template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradB {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = false, RELU = false;
-  typedef MCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
+template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradB : MCGeom<T, R, NW> {
+  typedef MCGeom<T, R, NW> G;
   const T* w; ConvGeo g; int NC;     // NC = output channels of the dgrad (= conv input channels)
-  int relu = 0;
-  unsigned lo[NIW]; bool cv[NIW]; int kr[NIW];
+  unsigned lo[G::NIW]; bool cv[G::NIW]; int kr[G::NIW];
   TapWalk tw;
   HD unsigned long bytes() const { return (unsigned long)g.SC * g.KH * g.KW * NC * sizeof(T); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX && 2 * g.SC >= BK; }
+  HD bool buf_ok() const { return bytes() < BUF_MAX && 2 * g.SC >= G::BK; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       kr[i] = G::krow(wave, i, lane); int cl = t0 + G::col(wave, i, lane);
       cv[i] = cl < NC;
       lo[i] = (unsigned)(((long)kr[i] * g.KH * g.KW * NC + cl) * sizeof(T));
     }
     tw = TapWalk{};
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
     const auto rs = make_rsrc(w, bytes());
     const int TW = g.ntw > 0 ? g.ntw : 1;
-    if (g.SC % BK) {                 // a tile spans taps tap .. tap+2 (rows c0+kr >= SC, >= 2 SC wrap)
-      tw.step_any(kt, BK, g.SC, TW);
+    if (g.SC % G::BK) {              // a tile spans taps tap .. tap+2 (rows c0+kr >= SC, >= 2 SC wrap)
+      tw.step_any(kt, G::BK, g.SC, TW);
       int th1, tw1, th2, tw2; tw.next_tap(TW, th1, tw1); TapWalk::tap_after(TW, th1, tw1, th2, tw2);
       const int kh = g.kh0 + g.s * tw.th, kw = g.kw0 + g.s * tw.tw;
       const int kh1 = g.kh0 + g.s * th1, kw1 = g.kw0 + g.s * tw1;
@@ -497,43 +404,40 @@ template <typename T, int R, int NW = GEMM_WAVES> struct ConvDgradB {
       const unsigned u1 = (unsigned)((((long)(tw.c0 - g.SC) * g.KH + kh1) * g.KW + kw1) * NC * sizeof(T));
       const unsigned u2 = (unsigned)((((long)(tw.c0 - 2 * g.SC) * g.KH + kh2) * g.KW + kw2) * NC * sizeof(T));
 #pragma unroll
-      for (int i = 0; i < NIW; i++) {
+      for (int i = 0; i < G::NIW; i++) {
         const int c = tw.c0 + kr[i];
         const int wr = (c >= g.SC) + (c >= 2 * g.SC);     // taps past the walker's: 0, 1 or (SC < BK) 2
         bool ok = cv[i] && (wr == 2 ? tv2 : wr ? tv1 : tv0);
-        sk(i, rs, ok ? lo[i] + (wr == 2 ? u2 : wr ? u1 : u0) : BUF_OOB);
+        blds16(rs, ok ? lo[i] + (wr == 2 ? u2 : wr ? u1 : u0) : BUF_OOB, d + i * 1024);
       }
       return;
     }
-    tw.step(kt, BK, g.SC, TW);
+    tw.step(kt, G::BK, g.SC, TW);
     const bool tv = tw.tap < g.nth * g.ntw;
     const int kh = g.kh0 + g.s * tw.th, kw = g.kw0 + g.s * tw.tw;
     const unsigned uo = (unsigned)((((long)tw.c0 * g.KH + kh) * g.KW + kw) * NC * sizeof(T));
 #pragma unroll
-    for (int i = 0; i < NIW; i++) sk(i, rs, (tv && cv[i]) ? lo[i] + uo : BUF_OOB);
+    for (int i = 0; i < G::NIW; i++) blds16(rs, (tv && cv[i]) ? lo[i] + uo : BUF_OOB, d + i * 1024);
   }
 };
 
 // wgrad B operand (MC gather): B[k=pix of the conv output grid RH x RW][n=(tap, cin)] = X[src][cin]
 // Fast path (RW % BK == 0): the 64 pixels of a K tile share one output row, so (b, oy, ox0) are
 // wave-uniform and interior tiles need no per-lane bounds test.
-template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct WgradB {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = false, RELU = RELU_;
-  typedef MCGeom<T, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
-  const T* x; ConvGeo g; int NPIX; int relu;   // g.SC = Cin of X, g.SH/SW = X dims, RH/RW = output grid
-  int kh[NIW], kw[NIW], kr[NIW], cin[NIW]; unsigned lo[NIW]; bool cval[NIW];
+template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct WgradB : MCGeom<T, R, NW, RELU_> {
+  typedef MCGeom<T, R, NW, RELU_> G;
+  const T* x; ConvGeo g;     // g.SC = Cin of X, g.SH/SW = X dims, RH/RW = output grid
+  int kh[G::NIW], kw[G::NIW], kr[G::NIW], cin[G::NIW]; unsigned lo[G::NIW]; bool cval[G::NIW];
   int nk, pb, poy, pox;                         // uniform walker (fast path)
-  int qb[NIW], qy[NIW], qx[NIW];                // per-lane walker (generic path)
+  int qb[G::NIW], qy[G::NIW], qx[G::NIW];                // per-lane walker (generic path)
   // the descriptor is rebased per K tile to the image of its first pixel (a tile of BK pixels
   // spans at most BK/hw + 2 images), so the batch itself may exceed 4 GiB
   HD unsigned long img_bytes() const { return (unsigned long)g.SH * g.SW * g.SC * sizeof(T); }
-  HD unsigned long bytes() const { return img_window_bytes(BK, g.RH * g.RW, g.B, img_bytes()); }
-  HD bool buf_ok() const { return bytes() < BUF_MAX; }
+  HD bool buf_ok() const { return img_window_bytes(G::BK, g.RH * g.RW, g.B, img_bytes()) < BUF_MAX; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       int col = t0 + G::col(wave, i, lane);
       kr[i] = G::krow(wave, i, lane);
       int tp = col / g.SC; cin[i] = col - tp * g.SC; kh[i] = tp / g.KW; kw[i] = tp - kh[i] * g.KW;
@@ -543,53 +447,52 @@ template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Wgr
     }
     nk = -1;
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
-    if (g.RW % BK == 0) {
-      if (kt != nk) { int k = kt * BK; int hw = g.RH * g.RW; pb = k / hw; int r = k - pb * hw; poy = r / g.RW; pox = r - poy * g.RW; }
-      else { pox += BK; if (pox >= g.RW) { pox = 0; if (++poy >= g.RH) { poy = 0; pb++; } } }
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
+    if (g.RW % G::BK == 0) {
+      if (kt != nk) { int k = kt * G::BK; int hw = g.RH * g.RW; pb = k / hw; int r = k - pb * hw; poy = r / g.RW; pox = r - poy * g.RW; }
+      else { pox += G::BK; if (pox >= g.RW) { pox = 0; if (++poy >= g.RH) { poy = 0; pb++; } } }
       nk = kt + 1;
       const int iy0 = poy * g.s - g.p, ix0 = pox * g.s - g.p;
       const bool live = pb < g.B;
       const auto rs = make_rsrc(x + (long)(live ? pb : 0) * g.SH * g.SW * g.SC, img_bytes());
       const unsigned uo = (unsigned)(((long)iy0 * g.SW + ix0) * g.SC * (long)sizeof(T));
-      const bool interior = iy0 >= 0 && iy0 + g.KH <= g.SH && ix0 >= 0 && ix0 + (BK - 1) * g.s + g.KW <= g.SW;
+      const bool interior = iy0 >= 0 && iy0 + g.KH <= g.SH && ix0 >= 0 && ix0 + (G::BK - 1) * g.s + g.KW <= g.SW;
       if (live && interior) {
 #pragma unroll
-        for (int i = 0; i < NIW; i++) sk(i, rs, cval[i] ? lo[i] + uo : BUF_OOB);
+        for (int i = 0; i < G::NIW; i++) blds16(rs, cval[i] ? lo[i] + uo : BUF_OOB, d + i * 1024);
       } else {
 #pragma unroll
-        for (int i = 0; i < NIW; i++) {
+        for (int i = 0; i < G::NIW; i++) {
           int iy = iy0 + kh[i], ix = ix0 + kr[i] * g.s + kw[i];
           bool ok = live && cval[i] && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
-          sk(i, rs, ok ? lo[i] + uo : BUF_OOB);
+          blds16(rs, ok ? lo[i] + uo : BUF_OOB, d + i * 1024);
         }
       }
       return;
     }
     // generic: per-lane pixel walker, descriptor rebased to the image of the tile's first pixel
     const int hw = g.RH * g.RW;
-    const int b0 = min(kt * BK / hw, g.B - 1);
+    const int b0 = min(kt * G::BK / hw, g.B - 1);
     const auto rs = make_rsrc(x + (long)b0 * g.SH * g.SW * g.SC, (unsigned long)(g.B - b0) * img_bytes());
     if (kt != nk) {
 #pragma unroll
-      for (int i = 0; i < NIW; i++) {
-        int k = kt * BK + kr[i];
+      for (int i = 0; i < G::NIW; i++) {
+        int k = kt * G::BK + kr[i];
         int b = k / hw; int r = k - b * hw; int oy = r / g.RW;
         qb[i] = b; qy[i] = oy; qx[i] = r - oy * g.RW;
       }
     }
     nk = kt + 1;
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       int iy = qy[i] * g.s - g.p + kh[i], ix = qx[i] * g.s - g.p + kw[i];
       bool ok = cval[i] && qb[i] < g.B && (unsigned)iy < (unsigned)g.SH && (unsigned)ix < (unsigned)g.SW;
       unsigned v = (unsigned)(((((long)(qb[i] - b0) * g.SH + iy) * g.SW + ix) * g.SC + cin[i]) * (long)sizeof(T));
-      sk(i, rs, ok ? v : BUF_OOB);
-      qx[i] += BK;
+      blds16(rs, ok ? v : BUF_OOB, d + i * 1024);
+      qx[i] += G::BK;
       while (qx[i] >= g.RW) { qx[i] -= g.RW; if (++qy[i] >= g.RH) { qy[i] = 0; qb[i]++; } }
     }
-    (void)NPIX;
   }
 };
 
@@ -598,40 +501,38 @@ template <typename T, int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Wgr
 // are one run of an image row and Cin % 256 == 0 puts a 256-column tile inside ONE tap, so the tile is a contiguous
 // 64-pixel run of x shifted by (dy, dx): per lane only its k-row and its channel offset are kept, the row / image
 // walk is uniform (scalar) and just the first / last pixel of a row can fall outside the image (dx = -1 / +1).
-template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Wgrad3B {
-  static constexpr int ROWS = R;
-  static constexpr bool KCL = false, RELU = RELU_;
-  typedef MCGeom<bf16, R, NW> G; static constexpr int NIW = G::NIW, BK = G::BK;
+template <int R, bool RELU_ = false, int NW = GEMM_WAVES> struct Wgrad3B : MCGeom<bf16, R, NW, RELU_> {
+  typedef MCGeom<bf16, R, NW, RELU_> G;
   const bf16* x; int B, H, W, Cin;
   int tdy, tdx;                                  // this block's tap offsets (uniform)
   int nk, pb, py, px0;                           // uniform walker: next K tile, its image / row / first column
-  int kr[NIW]; unsigned lo[NIW];
+  int kr[G::NIW]; unsigned lo[G::NIW];
   HD unsigned long img_bytes() const { return (unsigned long)H * W * Cin * 2; }
-  HD bool buf_ok() const { return img_bytes() < BUF_MAX && W % BK == 0 && Cin % 256 == 0; }
+  HD bool buf_ok() const { return img_bytes() < BUF_MAX && W % G::BK == 0 && Cin % 256 == 0; }
   DEV void setup(int t0, int tid) {
     const int lane = tid & 63, wave = wave_id();
     const int tap = t0 / Cin, c0 = t0 - tap * Cin;
     tdy = tap / 3 - 1; tdx = tap - 3 * (tap / 3) - 1;
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       kr[i] = G::krow(wave, i, lane);
       lo[i] = (unsigned)((kr[i] * Cin + c0 + G::col(wave, i, lane)) * 2);
     }
     nk = -1;
   }
-  DEV void issue(int kt, char* tile) { issue_to(kt, DmaSink{tile + wave_id() * NIW * 1024}); }
-  template <class SK> DEV void issue_to(int kt, SK sk) {
-    if (kt != nk) { const int p = kt * BK, hw = H * W; pb = p / hw; const int r = p - pb * hw; py = r / W; px0 = r - py * W; }
-    else { px0 += BK; if (px0 >= W) { px0 = 0; if (++py >= H) { py = 0; pb++; } } }
+  DEV void issue(int kt, char* tile) {
+    char* const d = G::dst(tile);
+    if (kt != nk) { const int p = kt * G::BK, hw = H * W; pb = p / hw; const int r = p - pb * hw; py = r / W; px0 = r - py * W; }
+    else { px0 += G::BK; if (px0 >= W) { px0 = 0; if (++py >= H) { py = 0; pb++; } } }
     nk = kt + 1;
     const int yy = py + tdy;
     const bool rowok = pb < B && (unsigned)yy < (unsigned)H;
     const auto rs = make_rsrc(x + (long)(rowok ? pb : 0) * H * W * Cin, img_bytes());
     const int base = ((yy * W + px0 + tdx) * Cin) * 2;          // pixel (yy, px0 + dx), channel 0 (may be < 0)
 #pragma unroll
-    for (int i = 0; i < NIW; i++) {
+    for (int i = 0; i < G::NIW; i++) {
       const bool ok = rowok && (unsigned)(px0 + kr[i] + tdx) < (unsigned)W;
-      sk(i, rs, ok ? (unsigned)(base + (int)lo[i]) : BUF_OOB);
+      blds16(rs, ok ? (unsigned)(base + (int)lo[i]) : BUF_OOB, d + i * 1024);
     }
   }
 };
@@ -642,6 +543,14 @@ DEV bf16x8 relu_frag(bf16x8 v) {
 DEV float relu_frag(float v) { return fmaxf(v, 0.f); }
 
 // ------------------------------------------------------------------ fragment readers
+// MC image -> bf16 MFMA operand: two ds_read_b64_tr_b16, the k rows of the fragment's low and high halves
+DEV bf16x8 read_tr_pair(const char* lo, const char* hi) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s4;
+  bf16x4 a = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)lo));
+  bf16x4 b = __builtin_bit_cast(bf16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)hi));
+  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+
 template <typename T, bool KCL, int R> struct Frag;
 
 template <int R> struct Frag<bf16, true, R> {     // KC: ds_read_b128
@@ -657,13 +566,7 @@ template <int R> struct Frag<bf16, false, R> {    // MC: 2 x ds_read_b64_tr_b16
     int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
     int byte = (row0 + 4 * p) * 2;
     int k0 = kk * 32 + 8 * g + q;
-    typedef __attribute__((address_space(3))) s16x4 lds_s4;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(lds + mc_off<RB>(k0, byte)));
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(lds + mc_off<RB>(k0 + 4, byte)));
-    bf16x8 r;
-    bf16x4 a = __builtin_bit_cast(bf16x4, lo), b = __builtin_bit_cast(bf16x4, hi);
-    r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = a[3]; r[4] = b[0]; r[5] = b[1]; r[6] = b[2]; r[7] = b[3];
-    return r;
+    return read_tr_pair(lds + mc_off<RB>(k0, byte), lds + mc_off<RB>(k0 + 4, byte));
   }
 };
 template <int R> struct Frag<float, true, R> {    // KC f32: lane -> A[row l&15][k = kk*4 + l>>4]
@@ -701,8 +604,7 @@ template <typename T, int BM, int BN, int NST_ = 3, int WM_ = 0> struct GemmShap
   static constexpr int STAGE = ABYTES + BBYTES;
   static constexpr int NST = NST_;
   static constexpr int LDT = BN + 4;                       // fp32 C-tile row stride
-  // the fp32 C tile is staged through LDS in row chunks of CROWS (half the tile when the whole
-  // tile would not fit beside the K stages, e.g. 256x256)
+  // the fp32 C tile is staged through LDS in row chunks of CROWS (half the tile where the whole would not fit: 256x256)
   static constexpr int CROWS = (BM * LDT * 4 <= NST * STAGE || BM * LDT * 4 <= 160 * 1024) ? BM : BM / 2;
   static constexpr int CBYTES = CROWS * LDT * 4;
   static constexpr int LDS = (NST * STAGE > CBYTES ? NST * STAGE : CBYTES);
@@ -715,18 +617,26 @@ template <typename T, int BM, int BN, int NST_ = 3, int WM_ = 0> struct GemmShap
   static_assert(MI >= 1 && NI >= 1 && TM % 16 == 0 && TN % 16 == 0, "bad wave tiling");
 };
 
-struct KRange { int kt0, kt1; };
+// block -> (M tile, N tile) of a 2-D grid: an XCD-contiguous linear index W (the blocks one XCD receives get
+// consecutive W), then row-major -- or, with G > 0, in groups of G M-tiles walked column-major, so the ~32 blocks an
+// XCD runs at once cover a G x (32 / G) patch and share G A-panels and 32 / G B-panels in that XCD's L2 instead of one
+// A-panel and 32 B-panels
+DEV void tile_of_block(int G, int& mt, int& nt) {
+  const int nN = gridDim.x, nM = gridDim.y, nwg = nN * nM;
+  const int L = blockIdx.y * nN + blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = L & 7, idx = L >> 3;
+  const int W = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+  if (G <= 0) { const unsigned uW = W, uN = gridDim.x; mt = uW / uN; nt = uW % uN; return; }     // (W >= 0: the cheaper division)
+  const int per = G * nN, g = W / per, w = W - g * per, m_first = g * G, gs = min(nM - m_first, G);
+  mt = m_first + w % gs; nt = w / gs;
+}
 
-// workgroup barrier that orders LDS only (does not drain in-flight global loads / LDS-DMA)
-
-// Block-level epilogue contract:  epi(tile, LDT, m0, n0, tid, BM, BN)
-//
-// Main loop: 3 LDS stages filled by LDS-DMA two K-tiles ahead; one raw s_barrier per K tile,
-// placed BEFORE the last k-step's MFMAs so the next tile's first fragments are read from LDS
-// while the current tile's last MFMAs run (fragments double-buffered in registers).
-// vmcnt is counted (the tile two steps ahead stays in flight across the barrier); there is
-// no __syncthreads() in the loop (it would drain vmcnt to 0: guide §5).
-// Block order is remapped so consecutive tiles of one row-panel share an XCD (guide T1).
+// Block-level epilogue contract:  epi(tile, LDT, m0, n0, tid, BM, BN, NT)
+// Main loop: NST LDS stages filled by LDS-DMA NST - 1 K tiles ahead; one raw s_barrier per K tile, placed BEFORE the
+// last k-step's MFMAs so the next tile's first fragments are read from LDS while the current tile's last MFMAs run
+// (fragments double-buffered in registers).  With NST = 3 vmcnt is counted (the tile two steps ahead stays in flight
+// across the barrier); there is no __syncthreads() in the loop (it would drain vmcnt to 0: guide §5).
+// Block order is remapped so consecutive tiles of one row-panel share an XCD (tile_of_block, guide T1).
 template <typename T, int BM, int BN, int NST, class LA, class LB, class EPI, int WM_ = 0>
 __global__ void __launch_bounds__(GEMM_THREADS) igemm_kernel(LA la, LB lb, EPI epi, int KTILES, int split) {
   typedef GemmShape<T, BM, BN, NST, WM_> S;
@@ -736,13 +646,7 @@ __global__ void __launch_bounds__(GEMM_THREADS) igemm_kernel(LA la, LB lb, EPI e
   constexpr int MI = S::MI, NI = S::NI, KS = Mma<T>::KSTEPS;
   constexpr int NL = LA::NIW + LB::NIW;       // LDS-DMA instructions per thread per K tile
   int bx, by;
-  {
-    const int nwg = gridDim.x * gridDim.y;
-    const int L = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = L & 7, idx = L >> 3;
-    const int W = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    bx = W % gridDim.x; by = W / gridDim.x;
-  }
+  tile_of_block(0, by, bx);
   const int m0 = by * BM, n0 = bx * BN;
   int per = (KTILES + split - 1) / split;
   int kt0 = blockIdx.z * per, kt1 = min(KTILES, kt0 + per);
@@ -849,10 +753,9 @@ __global__ void __launch_bounds__(GEMM_THREADS) igemm_kernel(LA la, LB lb, EPI e
   }
 }
 
-// iterate 8-wide row segments of the staged tile: f(m, n, const float* v8, r, c).  When the
-// thread count is a multiple of the segments per row (every config but the N=96 head), a thread
-// keeps ONE column group and the loop has a compile-time trip count, so it unrolls and the LDS
-// reads / global stores of all rows are in flight together.
+// iterate 8-wide row segments of the staged tile: f(m, n, const float* v8, r, c).  When the thread count is a multiple
+// of the segments per row (every config but the N=96 head), a thread keeps ONE column group and the loop has a
+// compile-time trip count, so it unrolls and the LDS reads / global stores of all rows are in flight together.
 template <class F> DEV void for_segments(const float* ct, int LDT, int BM, int BN, int m0, int n0, int M, int N, int tid, int NT, F f) {
   const int spr = BN / 8;
   if (NT % spr == 0 && BM % (NT / spr) == 0) {
@@ -1103,25 +1006,18 @@ struct EpiWgradPart {
 };
 
 // ------------------------------------------------------------------ 256x256 ping-pong kernel (bf16)
-// 8 waves = 2 (M) x 4 (N), each owning a 128x64 sub-tile (acc[8][4], 128 VGPRs); waves w and w+4
-// share a SIMD (cyclic wave->SIMD placement), so the two M halves are SIMD partners.  The M half
-// wr = 1 runs one barrier behind wr = 0: while one wave of a SIMD runs its 16-MFMA block, its
-// partner issues the next block's LDS reads and LDS-DMA (MI355X_MICROARCH.md "Two waves per SIMD",
-// cdna_hip_programming.md §5 "256² 8-phase template").
-//
-// Each K tile (BK = 64) is 4 phases = the wave's 4 C quadrants (64 rows x 32 cols) in the order
-// (0,0) (0,1) (1,1) (1,0); a phase is  [LDS reads | DMA issue] barrier [16 MFMA] barrier.  All of a
-// tile's fragments are read in its phases 0 and 1 (A0+B0, then B1+A1: 96 VGPRs), so its LDS buffer
-// is free from phase 3 on and the DMA of tile t+2 can start there, a whole tile ahead.
-// LDS: 2 buffers x 4 half images (A rows 0-127 / 128-255, B cols 0-127 / 128-255; 16 KB each), so
-// the loaders run with R = 128.  Tile t+1's A halves are issued in phase 3 of tile t-1 and its B
-// halves in phase 0 of tile t; phase 3 of tile t retires both with a counted vmcnt.
-//   RAW: every wave's wait for tile t+1 sits in its phase-3 load segment of tile t, i.e. before the
-//        barrier that precedes the first read of tile t+1 by either stagger half;
-//   WAR: a buffer's last reads are in phase 1; it is restaged in phase 3 (>= 2 phases later, so
-//        every reader's lgkmcnt(0) precedes a barrier the restaging wave has passed).
-// Fragment addressing inside a 128-row half image with every read's row0 a multiple of 16: the
-// per-lane part of the address is computed once and the row0 / kk parts become immediates.
+// 8 waves = 2 (M) x 4 (N), each a 128x64 sub-tile (acc[8][4], 128 VGPRs); waves w and w+4 share a SIMD, and the M half
+// wr = 1 runs one barrier behind wr = 0: while one wave of a SIMD runs its 16-MFMA block, its partner issues the next
+// block's LDS reads and LDS-DMA (MI355X_MICROARCH.md "Two waves per SIMD"; the schedule's rationale is in DESIGN.md).
+// A K tile (BK = 64) is 4 phases = the wave's 4 C quadrants (64 rows x 32 cols) in the order (0,0) (0,1) (1,1) (1,0); a
+// phase is  [LDS reads | DMA issue] barrier [16 MFMA] barrier.  All of a tile's fragments are read in phases 0 and 1
+// (A0+B0, then B1+A1: 96 VGPRs), so its LDS buffer (one of 2, each 4 half images of 16 KB: A rows 0-127 / 128-255, B
+// cols 0-127 / 128-255) is free from phase 3 on.  Phase 3 of tile t retires tile t+1's DMA with a counted vmcnt.
+//   RAW: every wave's wait for tile t+1 sits in its phase-3 load segment of tile t, i.e. before the barrier that
+//        precedes the first read of tile t+1 by either stagger half;
+//   WAR: a buffer's last reads are in phase 1; it is restaged in phase 3 (>= 2 phases later, so every reader's
+//        lgkmcnt(0) precedes a barrier the restaging wave has passed).
+// Fragment addresses inside a 128-row half image, row0 a multiple of 16: a per-lane part computed once + immediates
 //   KC [128][128 B]: kc_off(row0 + l, b) = row0*128 + kc_off(l, b)   ((r>>1)&7 depends on l only)
 //   MC [64 k][256 B]: mc_off<256>(kk*32 + 8g + q, 2*row0 + 8p)
 //                     = kk*8192 + (8g+q)*256 + 8p + (((row0>>4) ^ gk) << 5),  gk = q | (g&1)<<2
@@ -1142,21 +1038,13 @@ template <> struct PPFrag<false> {
     base = (8 * g + q) * 256 + 8 * p; gk = (q | ((g & 1) << 2)) ^ (h64 << 2);
   }
   DEV bf16x8 read(const char* img, int row0, int kk) const {
-    typedef __attribute__((address_space(3))) s16x4 lds_s4;
     const char* a = img + base + ((((row0 >> 4) ^ gk)) << 5) + kk * 8192;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)a);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(a + 1024));
-    bf16x4 x = __builtin_bit_cast(bf16x4, lo), y = __builtin_bit_cast(bf16x4, hi);
-    bf16x8 r;
-    r[0] = x[0]; r[1] = x[1]; r[2] = x[2]; r[3] = x[3]; r[4] = y[0]; r[5] = y[1]; r[6] = y[2]; r[7] = y[3];
-    return r;
+    return read_tr_pair(a, a + 1024);
   }
 };
 
-
-// The epilogue stages C through the K-stage LDS in two 128-row chunks with LDS barriers only (a
-// __syncthreads() would drain the stores).  (A persistent variant -- the next tile's first K
-// stage issued behind this tile's stores -- measured within 5 % of this at 20 spilled VGPRs.)
+// The epilogue stages C through the K-stage LDS in two rounds of two 64-row quarters with LDS barriers only (a
+// __syncthreads() would drain the stores).
 // Dev timeline build (-DS3OD_TIMELINE, tools/pp_timeline.py; never in the production library): the ping-pong kernel
 // records per block [start, main loop done, epilogue done, HW_ID / XCC_ID, C half 0 staged, half 0 done, half 1
 // staged, -] (s_memrealtime, 100 MHz) into s3od_tl[linear block][8], set per translation unit by s3od_dbg_timeline()
@@ -1167,20 +1055,6 @@ static __device__ unsigned long long* s3od_tl;
 #else
 #define S3OD_TL(slot, v) do { } while (0)
 #endif
-
-// block -> (M tile, N tile) of a 2-D grid: an XCD-contiguous linear index W (the blocks one XCD receives get
-// consecutive W), then row-major -- or, with G > 0, in groups of G M-tiles walked column-major, so the ~32 blocks an
-// XCD runs at once cover a G x (32 / G) patch and share G A-panels and 32 / G B-panels in that XCD's L2 instead of one
-// A-panel and 32 B-panels
-DEV void tile_of_block(int G, int& mt, int& nt) {
-  const int nN = gridDim.x, nM = gridDim.y, nwg = nN * nM;
-  const int L = blockIdx.y * nN + blockIdx.x;
-  const int q = nwg >> 3, r = nwg & 7, xcd = L & 7, idx = L >> 3;
-  const int W = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-  if (G <= 0) { mt = W / nN; nt = W % nN; return; }
-  const int per = G * nN, g = W / per, w = W - g * per, m_first = g * G, gs = min(nM - m_first, G);
-  mt = m_first + w % gs; nt = w / gs;
-}
 
 template <class LA, class LB, class EPI>
 __global__ void __launch_bounds__(GEMM_THREADS, 1) igemm_pp_kernel(LA la0, LB lb0, EPI epi, int KTILES, int split, int flags) {
@@ -1258,12 +1132,11 @@ __global__ void __launch_bounds__(GEMM_THREADS, 1) igemm_pp_kernel(LA la0, LB lb
       __builtin_amdgcn_s_setprio(0);
       raw_barrier();
     };
-    // DMA issue spread over the four load segments (round 5 issued both B halves in phase 0 and both A halves in
-    // phase 3, making those load segments outlast the partner's 16 MFMAs): B half 0 / 1 of tile t+1 in phases 0 / 1
-    // (their buffer's last reads were in tile t-1); A half 0 of tile t+2 in phase 2 -- read only by the wr = 0 waves,
-    // whose last reads (phase 1) every wave has waited for before the barrier that opens its phase 2; A half 1 in
-    // phase 3 -- read by the wr = 1 waves, which wait for their phase-1 reads one barrier later, still before any
-    // wave's phase 3.
+    // DMA issue spread over the four load segments, so none outlasts the partner's 16 MFMAs: B half 0 / 1 of tile t+1
+    // in phases 0 / 1 (their buffer's last reads were in tile t-1); A half 0 of tile t+2 in phase 2 -- read only by
+    // the wr = 0 waves, whose last reads (phase 1) every wave has waited for before the barrier that opens its phase
+    // 2; A half 1 in phase 3 -- read by the wr = 1 waves, which wait for their phase-1 reads one barrier later, still
+    // before any wave's phase 3.
     for (int t = 0; t < nt; ++t) {
       char* cb = smem + (t & 1) * STG;
       char* nb = smem + ((t + 1) & 1) * STG;
@@ -1291,12 +1164,10 @@ __global__ void __launch_bounds__(GEMM_THREADS, 1) igemm_pp_kernel(LA la0, LB lb
   vm_drain();
   // The C tile goes through LDS (fp32) in two rounds of two 64-row quarters: round c stages rows [c*64, c*64+64) of
   // each wave row half (wave row wr -> buffer wr), then the epilogue runs on both.  After round 0 every wave's first
-  // four accumulator row tiles are dead, so at most 64 accumulator VGPRs are live under the epilogue code (halves
-  // staged one at a time kept the wr = 1 waves' 128 live through half 0's epilogue).
+  // four accumulator row tiles are dead, so at most 64 accumulator VGPRs are live under the epilogue code.  (A lambda
+  // on a compile-time round, not a loop: a loop this size stays rolled and indexes acc at run time: acc on the stack.)
   float* ct0 = (float*)smem;
   float* ct1 = ct0 + 64 * LDT;
-  // (a lambda on a compile-time round, not a loop: a loop this size stays rolled and indexes acc at run time,
-  // which puts all of acc on the stack)
   auto round = [&](auto CC) {
     constexpr int c = decltype(CC)::value;
     lds_barrier();
@@ -1339,120 +1210,6 @@ __global__ void __launch_bounds__(GEMM_THREADS, 1) igemm_pp_kernel(LA la0, LB lb
 }
 constexpr int PP_LDS = 128 * (256 + 4) * 4;   // two 64-row C quarters (133 KB) >= the two 64 KB K stages
 
-// ------------------------------------------------------------------ k-step images of the 4-wave kernel (gemm_q.hip)
-// The 4-wave kernel stages ONE 32-deep k-step of an operand per LDS image: 256 rows x 64 B = 16 KB = 16 LDS-DMA pieces
-// of 1 KiB, four per wave (piece = wave * 4 + i).
-//   KC image [256 rows][64 B]: four rows share a 256-B bank row, so the 16-B chunk c of row r sits at physical chunk
-//     c ^ kc64_x(r), kc64_x = (0, 3, 2, 1)[(r >> 2) & 3].  A fragment read (lane (g, l): row row0 + l, chunk g) is then
-//     conflict-free: ds_read_b128 serves lanes {g = 0: l 0-3, 12-15; g = 1: l 4-11} (and the three like groups)
-//     together, i.e. per l & 3 the four (g, l >> 2) pairs (0,0) (0,3) (1,1) (1,2), whose physical chunks
-//     g ^ kc64_x are 0, 1, 2, 3.  Piece p, lane j: row p * 16 + (j >> 2), physical chunk j & 3 -- the same XOR
-//     on the DMA source offset and on the read (guide §5.4 rule 21).
-//   MC image [32 k][512 B]: the k rows kk * 32 .. + 31 of the 64-deep MC tile image, swizzle unchanged (g(k) only
-//     depends on k & 3 and (k >> 3) & 1, both k-step-local).  Piece p, lane j: k row p * 2 + (j >> 5), physical byte
-//     (j & 31) * 16.
-DEV int kc64_x(int r) { const int h = (r >> 2) & 3; return h ^ ((h & 1) << 1); }
-// The pieces are issued by inline asm, descriptor built by hand (base, stride 0, bytes, raw-buffer flags -- the words
-// make_rsrc's builtin produces): the waitcnt pass does not see them, so it adds no vmcnt(0) of its own in front of LDS
-// reads it cannot tell from the DMA's target (it does in front of every ds_read_b64_tr_b16, which would drain the
-// ring); the kernel's counted waits order them.  The asm sets M0 (the wave's LDS base) itself: nothing else in these
-// kernels uses M0.
-typedef __attribute__((address_space(3))) const char lds_cchar;
-DEV unsigned lds_addr(const char* p) { return (unsigned)(unsigned long)(lds_cchar*)p; }
-DEV const char* lds_ptr(unsigned a) { return (const char*)(lds_cchar*)(unsigned long)a; }
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-DEV i32x4_t q_rsrc(const void* p, unsigned long bytes) {
-  const unsigned long a = (unsigned long)p;
-  return i32x4_t{(int)(unsigned)a, (int)((a >> 32) & 0xffff), (int)(unsigned)(bytes < BUF_MAX ? bytes : BUF_MAX), 0x00020000};
-}
-DEV void blds16s(i32x4_t r, unsigned voff, unsigned soff, unsigned lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
-               :: "v"(voff), "s"(r), "s"(soff), "s"(lds_wave_base) : "memory");
-}
-// klim = the end of the block's K range (K, or the end of its split-K share): k-steps at or past it are staged as
-// zeros without touching memory, by a descriptor of zero bytes (scalar).
-template <class L, bool KCL = L::KCL> struct KStep;
-template <class L> struct KStep<L, true> {          // over DenseKC<bf16, 256, 4>
-  const bf16* pb; unsigned long nb; unsigned vo[4], vt[4]; int wb, klim, kpart;
-  DEV void setup(const L& l, int t0, int tid, int klim_) {
-    const int lane = tid & 63, wave = wave_id(), rem = l.nrows - t0;
-    wb = wave * 4096;
-    klim = klim_;
-    kpart = (klim & 31) ? klim >> 5 : -1;           // the k-step that klim cuts (K % 32 != 0), if any
-    pb = l.p + (long)t0 * l.ld;
-    nb = rem > 0 ? ((unsigned long)(min(rem, 256) - 1) * l.ld + l.K) * 2 : 0;
-    const int kel = ((lane & 3) ^ kc64_x(lane >> 2)) * 8;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int r = (wave * 4 + i) * 16 + (lane >> 2);
-      vo[i] = r < rem ? (unsigned)(((long)r * l.ld + kel) * 2) : BUF_OOB;
-      vt[i] = (klim & ~31) + kel < klim ? vo[i] : BUF_OOB;     // offsets for k-step kpart: chunks past K read zeros
-    }
-  }
-  // piece i of k-step ks into the image at img; the k-step's byte offset rides in the scalar offset
-  DEV void piece(const L&, int ks, char* img, int i) const {
-    const auto rs = q_rsrc(pb, ks * 32 < klim ? nb : 0);
-    blds16s(rs, ks == kpart ? vt[i] : vo[i], (unsigned)ks * 64u, lds_addr(img) + wb + i * 1024);
-  }
-};
-template <class L> struct KStep<L, false> {         // over DenseMC<bf16, 256, 4>
-  unsigned vo[4]; int wb; unsigned long tot;
-  DEV void setup(const L& l, int t0, int tid, int klim) {
-    const int lane = tid & 63, wave = wave_id();
-    wb = wave * 4096;
-    // bytes up to the end of k row klim - 1: the range check zero-fills every later row, no per-lane K-tail test
-    tot = klim > 0 ? ((unsigned long)(klim - 1) * l.ld + l.ncols) * 2 : 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int k = wave * 8 + (lane >> 5) + 2 * i;
-      const int cl = t0 + mc_logical_byte<512>(k, (lane & 31) * 16) / 2;
-      vo[i] = cl < l.ncols ? (unsigned)(((long)k * l.ld + cl) * 2) : BUF_OOB;
-    }
-  }
-  // the descriptor is rebased to the k-step's first row, as DenseMC rebases it per K tile
-  DEV void piece(const L& l, int ks, char* img, int i) const {
-    const unsigned long e0 = (unsigned long)ks * 32 * l.ld * 2;
-    const auto rs = q_rsrc((const char*)l.p + e0, e0 < tot ? tot - e0 : 0);
-    blds16s(rs, vo[i], 0u, lds_addr(img) + wb + i * 1024);
-  }
-};
-// Fragment reads of a k-step image inside the ring of four 32 KB stages.  The per-lane address is computed once; the
-// row block (i * 16 rows) and the stage's place inside its PAIR of stages (st01 * 32 KB) are immediates.  A DS offset
-// field holds 16 bits, so the pair (stages 0-1 / 2-3) is in the address register: flip() moves it to the other pair
-// (one VALU per address register and pair of k-steps).
-template <bool KCL> struct QFrag;
-template <> struct QFrag<true> {
-  unsigned a;
-  DEV void init(const char* img, int lane, int half) {
-    const int l = lane & 15;
-    a = lds_addr(img) + half * 8192 + l * 64 + (((lane >> 4) ^ kc64_x(l)) << 4);
-  }
-  DEV void flip(int d) { a += d; }
-  DEV bf16x8 read(int st01, int i) const { return *(const bf16x8*)(lds_ptr(a) + st01 * 32768 + i * 1024); }
-};
-template <> struct QFrag<false> {
-  unsigned a[8];
-  DEV void init(const char* img, int lane, int half) {
-    const int g = lane >> 4, l = lane & 15, q = l >> 2, p = l & 3, gk = q | ((g & 1) << 2);
-#pragma unroll
-    for (int i = 0; i < 8; i++) a[i] = lds_addr(img) + (8 * g + q) * 512 + half * 256 + ((i ^ gk) << 5) + 8 * p;
-  }
-  DEV void flip(int d) {
-#pragma unroll
-    for (int i = 0; i < 8; i++) a[i] += d;
-  }
-  DEV bf16x8 read(int st01, int i) const {
-    typedef __attribute__((address_space(3))) s16x4 lds_s4;
-    const char* s = lds_ptr(a[i]) + st01 * 32768;
-    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)s);
-    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(s + 2048));
-    bf16x4 x = __builtin_bit_cast(bf16x4, lo), y = __builtin_bit_cast(bf16x4, hi);
-    bf16x8 r;
-    r[0] = x[0]; r[1] = x[1]; r[2] = x[2]; r[3] = x[3]; r[4] = y[0]; r[5] = y[1]; r[6] = y[2]; r[7] = y[3];
-    return r;
-  }
-};
-
 // the 4-wave 256x256 kernel (gemm_q.hip, its own translation unit: AGPR accumulators); instantiated there for the
 // linears' (loader, epilogue) combinations
 template <class LA, class LB, class EPI>
@@ -1464,30 +1221,29 @@ static int launch_igemm(LA la, LB lb, EPI epi, int M, int N, int KTILES, int spl
   if constexpr (WM_ < 0) {
     static_assert(BM == 256 && BN == 256 && sizeof(T) == 2, "q config");
     return launch_igemm_q(la, lb, epi, M, N, KTILES, split, zdim_extra, st);
-  } else if constexpr (LA::ROWS * 2 == BM) {    // half-row loaders: the 256x256 ping-pong kernel
-    static_assert(BM == 256 && BN == 256 && LB::ROWS == 128 && sizeof(T) == 2, "ping-pong config");
-    if (!la.buf_ok() || !lb.buf_ok()) {
-      s3od_set_error("igemm: operand window too large for a buffer descriptor or gather channels < %d", KT<T>::BK / 2);
-      return 22;
-    }
-    auto kfn = igemm_pp_kernel<LA, LB, EPI>;
-    static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS), true);   // once per process (thread-safe static init)
-    (void)attr;
-    const int flags = S3OD_KNOB("S3OD_PP_FLAGS", 0) | (S3OD_KNOB("S3OD_GEMM_GROUP", 0) & 0xff) << 8;
-    dim3 grid(cdiv(N, BN), cdiv(M, BM), split * zdim_extra);
-    hipLaunchKernelGGL(kfn, grid, dim3(GEMM_THREADS), PP_LDS, st, la, lb, epi, KTILES, split, flags);
-    return s3od_check_launch("igemm_pp");
   } else {
+    constexpr bool PP = LA::ROWS * 2 == BM;       // half-row loaders: the 256x256 ping-pong kernel
+    static_assert(!PP || (BM == 256 && BN == 256 && LB::ROWS == 128 && sizeof(T) == 2), "ping-pong config");
     if (!la.buf_ok() || !lb.buf_ok()) {
       s3od_set_error("igemm: operand window too large for a buffer descriptor or gather channels < %d", KT<T>::BK / 2);
       return 22;
     }
-    typedef GemmShape<T, BM, BN, NST, WM_> S;
-    auto kfn = igemm_kernel<T, BM, BN, NST, LA, LB, EPI, WM_>;
-    static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS), true);   // once per process (thread-safe static init)
-    (void)attr;
-    dim3 grid(cdiv(N, BN), cdiv(M, BM), split * zdim_extra);
-    hipLaunchKernelGGL(kfn, grid, dim3(GEMM_THREADS), S::LDS, st, la, lb, epi, KTILES, split);
-    return s3od_check_launch("igemm");
+    const dim3 grid(cdiv(N, BN), cdiv(M, BM), split * zdim_extra);
+    // (the attribute is set once per process: thread-safe static initialisation)
+    if constexpr (PP) {
+      auto kfn = igemm_pp_kernel<LA, LB, EPI>;
+      static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS), true);
+      (void)attr;
+      const int flags = S3OD_KNOB("S3OD_PP_FLAGS", 0) | (S3OD_KNOB("S3OD_GEMM_GROUP", 0) & 0xff) << 8;
+      hipLaunchKernelGGL(kfn, grid, dim3(GEMM_THREADS), PP_LDS, st, la, lb, epi, KTILES, split, flags);
+      return s3od_check_launch("igemm_pp");
+    } else {
+      typedef GemmShape<T, BM, BN, NST, WM_> S;
+      auto kfn = igemm_kernel<T, BM, BN, NST, LA, LB, EPI, WM_>;
+      static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS), true);
+      (void)attr;
+      hipLaunchKernelGGL(kfn, grid, dim3(GEMM_THREADS), S::LDS, st, la, lb, epi, KTILES, split);
+      return s3od_check_launch("igemm");
+    }
   }
 }

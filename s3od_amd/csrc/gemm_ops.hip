@@ -1,7 +1,8 @@
 // Hand-pipelined conv kernels with counted vmcnt waits: the register-weight 3x3 / ConvTranspose / strided convs, the
 // register-staged halo weight gradient and the 4x4 s2 LDS-DMA weight gradient, with their launchers and shape
-// predicates (declared in gemm.hpp; the entries that route to them are in conv_ops.hip).
+// predicates (declared in conv_kernels.hpp; the entries that route to them are in conv_ops.hip).
 #include "gemm.hpp"
+#include "conv_kernels.hpp"
 
 // ---------------------------------------------------------------- register-weight 3x3 conv, 64 -> 64
 // The full-resolution 64-channel convs (upsample_2x.2 forward and its stride-1 data gradient) move

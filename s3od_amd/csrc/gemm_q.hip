@@ -8,7 +8,7 @@
 // A 128x128 wave tile halves the fragment reads per MFMA (each A / B fragment feeds 8 MFMAs instead of 4).
 //
 // K loop: a ring of four LDS stages, one 32-deep k-step (64 MFMAs per wave) each: A 256 x 64 B | B 256 x 64 B = 32 KB
-// (images and loaders: gemm.hpp KStep / QFrag).  K-step s computes from fragment buffer s & 1 and, INSIDE its MFMA
+// (images and loaders: KStep / QFrag below).  K-step s computes from fragment buffer s & 1 and, INSIDE its MFMA
 // stream, reads the fragments of k-step s + 1 (stage (s + 1) & 3) into the other buffer and issues the LDS-DMA of
 // k-step s + 4 into its own stage s & 3:
 //   lgkmcnt(0)                  this k-step's fragments (read a whole block ago) are in
@@ -27,6 +27,112 @@
 // Epilogue: the fp32 C tile is staged through the (free) ring LDS in two 128-row halves and handed to the same
 // block-level epilogue functors as the other kernels (NT = 256 threads).
 #include "gemm.hpp"
+
+// ------------------------------------------------------------------ k-step images: loaders and fragment readers
+// ONE 32-deep k-step of an operand per LDS image: 256 rows x 64 B = 16 LDS-DMA pieces of 1 KiB, piece = wave * 4 + i.
+//   KC image [256 rows][64 B]: four rows share a 256-B bank row, so the 16-B chunk c of row r sits at physical chunk
+//     c ^ kc64_x(r), kc64_x = (0, 3, 2, 1)[(r >> 2) & 3].  A fragment read (lane (g, l): row row0 + l, chunk g) is then
+//     conflict-free: ds_read_b128 serves lanes {g = 0: l 0-3, 12-15; g = 1: l 4-11} (and the three like groups)
+//     together, i.e. per l & 3 the four (g, l >> 2) pairs (0,0) (0,3) (1,1) (1,2), whose physical chunks g ^ kc64_x are
+//     0, 1, 2, 3.  Piece p, lane j: row p * 16 + (j >> 2), physical chunk j & 3 -- the same XOR on the DMA source
+//     offset and on the read (guide §5.4 rule 21).
+//   MC image [32 k][512 B]: the k rows kk * 32 .. + 31 of the 64-deep MC tile image, swizzle unchanged (g(k) depends on
+//     k & 3 and (k >> 3) & 1 only, both k-step-local).  Piece p, lane j: k row p * 2 + (j >> 5), byte (j & 31) * 16.
+DEV int kc64_x(int r) { const int h = (r >> 2) & 3; return h ^ ((h & 1) << 1); }
+// The pieces are issued by inline asm, descriptor built by hand (base, stride 0, bytes, raw-buffer flags -- the words
+// make_rsrc's builtin produces): the waitcnt pass does not see them, so it adds no vmcnt(0) of its own in front of LDS
+// reads it cannot tell from the DMA's target (it does in front of every ds_read_b64_tr_b16, which would drain the
+// ring); the kernel's counted waits order them.  The asm sets M0 (the wave's LDS base) itself: nothing else in these
+// kernels uses M0.
+typedef __attribute__((address_space(3))) const char lds_cchar;
+DEV unsigned lds_addr(const char* p) { return (unsigned)(unsigned long)(lds_cchar*)p; }
+DEV const char* lds_ptr(unsigned a) { return (const char*)(lds_cchar*)(unsigned long)a; }
+typedef int i32x4_t __attribute__((ext_vector_type(4)));
+DEV i32x4_t q_rsrc(const void* p, unsigned long bytes) {
+  const unsigned long a = (unsigned long)p;
+  return i32x4_t{(int)(unsigned)a, (int)((a >> 32) & 0xffff), (int)(unsigned)(bytes < BUF_MAX ? bytes : BUF_MAX), 0x00020000};
+}
+DEV void blds16s(i32x4_t r, unsigned voff, unsigned soff, unsigned lds_wave_base) {
+  asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds"
+               :: "v"(voff), "s"(r), "s"(soff), "s"(lds_wave_base) : "memory");
+}
+// klim = the end of the block's K range (K, or the end of its split-K share): k-steps at or past it are staged as
+// zeros without touching memory, by a descriptor of zero bytes (scalar).
+template <class L, bool KCL = L::KCL> struct KStep;
+template <class L> struct KStep<L, true> {          // over DenseKC<bf16, 256, 4>
+  const bf16* pb; unsigned long nb; unsigned vo[4], vt[4]; int wb, klim, kpart;
+  DEV void setup(const L& l, int t0, int tid, int klim_) {
+    const int lane = tid & 63, wave = wave_id(), rem = l.nrows - t0;
+    wb = wave * 4096;
+    klim = klim_;
+    kpart = (klim & 31) ? klim >> 5 : -1;           // the k-step that klim cuts (K % 32 != 0), if any
+    pb = l.p + (long)t0 * l.ld;
+    nb = rem > 0 ? ((unsigned long)(min(rem, 256) - 1) * l.ld + l.K) * 2 : 0;
+    const int kel = ((lane & 3) ^ kc64_x(lane >> 2)) * 8;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = (wave * 4 + i) * 16 + (lane >> 2);
+      vo[i] = r < rem ? (unsigned)(((long)r * l.ld + kel) * 2) : BUF_OOB;
+      vt[i] = (klim & ~31) + kel < klim ? vo[i] : BUF_OOB;     // offsets for k-step kpart: chunks past K read zeros
+    }
+  }
+  // piece i of k-step ks into the image at img; the k-step's byte offset rides in the scalar offset
+  DEV void piece(const L&, int ks, char* img, int i) const {
+    const auto rs = q_rsrc(pb, ks * 32 < klim ? nb : 0);
+    blds16s(rs, ks == kpart ? vt[i] : vo[i], (unsigned)ks * 64u, lds_addr(img) + wb + i * 1024);
+  }
+};
+template <class L> struct KStep<L, false> {         // over DenseMC<bf16, 256, 4>
+  unsigned vo[4]; int wb; unsigned long tot;
+  DEV void setup(const L& l, int t0, int tid, int klim) {
+    const int lane = tid & 63, wave = wave_id();
+    wb = wave * 4096;
+    // bytes up to the end of k row klim - 1: the range check zero-fills every later row, no per-lane K-tail test
+    tot = klim > 0 ? ((unsigned long)(klim - 1) * l.ld + l.ncols) * 2 : 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int k = wave * 8 + (lane >> 5) + 2 * i;
+      const int cl = t0 + mc_logical_byte<512>(k, (lane & 31) * 16) / 2;
+      vo[i] = cl < l.ncols ? (unsigned)(((long)k * l.ld + cl) * 2) : BUF_OOB;
+    }
+  }
+  // the descriptor is rebased to the k-step's first row, as DenseMC rebases it per K tile
+  DEV void piece(const L& l, int ks, char* img, int i) const {
+    const unsigned long e0 = (unsigned long)ks * 32 * l.ld * 2;
+    const auto rs = q_rsrc((const char*)l.p + e0, e0 < tot ? tot - e0 : 0);
+    blds16s(rs, vo[i], 0u, lds_addr(img) + wb + i * 1024);
+  }
+};
+// Fragment reads of a k-step image inside the ring of four 32 KB stages.  The per-lane address is computed once; the
+// row block (i * 16 rows) and the stage's place inside its PAIR of stages (st01 * 32 KB) are immediates.  A DS offset
+// field holds 16 bits, so the pair (stages 0-1 / 2-3) is in the address register: flip() moves it to the other pair
+// (one VALU per address register and pair of k-steps).
+template <bool KCL> struct QFrag;
+template <> struct QFrag<true> {
+  unsigned a;
+  DEV void init(const char* img, int lane, int half) {
+    const int l = lane & 15;
+    a = lds_addr(img) + half * 8192 + l * 64 + (((lane >> 4) ^ kc64_x(l)) << 4);
+  }
+  DEV void flip(int d) { a += d; }
+  DEV bf16x8 read(int st01, int i) const { return *(const bf16x8*)(lds_ptr(a) + st01 * 32768 + i * 1024); }
+};
+template <> struct QFrag<false> {
+  unsigned a[8];
+  DEV void init(const char* img, int lane, int half) {
+    const int g = lane >> 4, l = lane & 15, q = l >> 2, p = l & 3, gk = q | ((g & 1) << 2);
+#pragma unroll
+    for (int i = 0; i < 8; i++) a[i] = lds_addr(img) + (8 * g + q) * 512 + half * 256 + ((i ^ gk) << 5) + 8 * p;
+  }
+  DEV void flip(int d) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) a[i] += d;
+  }
+  DEV bf16x8 read(int st01, int i) const {
+    const char* s = lds_ptr(a[i]) + st01 * 32768;
+    return read_tr_pair(s, s + 2048);
+  }
+};
 
 namespace {
 constexpr int Q_THREADS = 256, Q_BM = 256, Q_BN = 256, Q_IMG = 256 * 64, Q_STAGE = 2 * Q_IMG, Q_RING = 4, Q_LDT = Q_BN + 4;

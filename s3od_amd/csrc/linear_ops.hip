@@ -186,7 +186,7 @@ static int launch_tail_gemm(const LA& la, const LB& lb, EPI e, int M, int N, hip
 template <typename T, class C, class LA, class LB, class EPI>
 static int launch_op(LA la, LB lb, EPI e, int M, int N, int KTILES, bool tail, hipStream_t st) {
   if constexpr (!C::PP && sizeof(T) == 2 && LA::KCL)
-    if (tail && !la.relu && !lb.relu && !S3OD_OFF("S3OD_TAIL_SKINNY"))
+    if (tail && !LA::RELU && !LB::RELU && !S3OD_OFF("S3OD_TAIL_SKINNY"))
       return launch_tail_gemm(la, lb, e, M, N, st);
   return launch_igemm<T, C::BM, C::BN, LA, LB, EPI, C::NST, C::WM>(la, lb, e, M, N, KTILES, 1, 1, st);
 }
@@ -209,8 +209,8 @@ static int linear_fwd_rows(int dtype, int M, int N, int K, const void* x, long l
       // DPT projections M=65536 K=768 run on it too (tools/lib_ab.py: N 1024 160 -> 156 us, 512 90 -> 87, 256 54 -> 52)
       const int def = (pp_pays(M, N) && N % 256 == 0) ? 5 : (K >= 2048 ? 0 : 1);
       return with_cfg<T, true>(def, tail, [&](auto C) -> int {
-        DenseKC<T, decltype(C)::LM, decltype(C)::W> la{(const T*)x, ldx, M, K, 0};
-        DenseKC<T, decltype(C)::LN, decltype(C)::W> lb{(const T*)w, (long)K, N, K, 0};
+        DenseKC<T, decltype(C)::LM, decltype(C)::W> la{{}, (const T*)x, ldx, M, K};
+        DenseKC<T, decltype(C)::LN, decltype(C)::W> lb{{}, (const T*)w, (long)K, N, K};
         EpiStd<TO, TR, T> e{(TO*)out, ldo, 0, bias, scale, shift, (const TR*)res1, ldr1, (const TR*)res2, ldr2,
                             (T*)pre, ldp, nullptr, act, M, N, rm};
         return launch_op<T, decltype(C)>(la, lb, e, M, N, KTILES, tail, st);
@@ -246,8 +246,8 @@ static int linear_dgrad_rows(int dtype, int M, int N, int K, const void* dy, lon
     // (o_proj 118 vs 118 us)
     const int def = (pp_pays(M, N) && N % 256 == 0 && (K >= 2048 || act != ACT_NONE)) ? 5 : 1;
     return with_cfg<T, true>(def, tail, [&](auto C) -> int {
-      DenseKC<T, decltype(C)::LM, decltype(C)::W> la{(const T*)dy, lddy, M, K, 0};
-      DenseMC<T, decltype(C)::LN, decltype(C)::W> lb{(const T*)w, (long)N, K, N};
+      DenseKC<T, decltype(C)::LM, decltype(C)::W> la{{}, (const T*)dy, lddy, M, K};
+      DenseMC<T, decltype(C)::LN, decltype(C)::W> lb{{}, (const T*)w, (long)N, K, N};
       if (out_f32) {
         // f32 output: aux is an f32 tensor to add (e.g. the residual-stream gradient, in place)
         EpiStd<float, float> e{(float*)dx, lddx, 0, nullptr, nullptr, nullptr, (const float*)aux, ldaux, nullptr, 0, nullptr, 0, nullptr, act, M, N, rm, colsum};
@@ -346,8 +346,8 @@ int s3od_linear_wgrad(int dtype, int Nout, int Kin, int rows, const void* dy, lo
     const int KTILES = cdiv(rows, KT<T>::BK);
     return linear_wgrad_route<T>(Nout, Kin, rows, split, [&](auto C, int sp, long slab_floats) -> int {
       constexpr int BM = decltype(C)::BM, BN = decltype(C)::BN, NST = decltype(C)::NST;
-      DenseMC<T, decltype(C)::LM, decltype(C)::W> la{(const T*)dy, lddy, rows, Nout};
-      DenseMC<T, decltype(C)::LN, decltype(C)::W> lb{(const T*)x, ldx, rows, Kin};
+      DenseMC<T, decltype(C)::LM, decltype(C)::W> la{{}, (const T*)dy, lddy, rows, Nout};
+      DenseMC<T, decltype(C)::LN, decltype(C)::W> lb{{}, (const T*)x, ldx, rows, Kin};
       if constexpr (decltype(C)::SLAB) {
         if (slab && slab_floats > 0 && slab_bytes >= 4 * slab_floats) {
           EpiWgradPart e{slab, Nout, Kin};
@@ -372,8 +372,8 @@ int s3od_qkv_rope_fwd(int dtype, int B, int Ntok, int P, int H, const void* x, c
   DISPATCH_T(dtype, {
     return for_row_panels(B * Ntok, 0, [&](int m_first, int M, bool tail) -> int {
       return with_cfg<T>(pp_pays(M, N) ? 5 : 1, tail, [&](auto C) -> int {
-        DenseKC<T, decltype(C)::LM, decltype(C)::W> la{(const T*)x + (long)m_first * D, (long)D, M, D, 0};
-        DenseKC<T, decltype(C)::LN, decltype(C)::W> lb{(const T*)w, (long)D, N, D, 0};
+        DenseKC<T, decltype(C)::LM, decltype(C)::W> la{{}, (const T*)x + (long)m_first * D, (long)D, M, D};
+        DenseKC<T, decltype(C)::LN, decltype(C)::W> lb{{}, (const T*)w, (long)D, N, D};
         EpiQKV<T> e{(T*)q, (T*)k, (T*)v, bias, cos_t, sin_t, M, Ntok, P, H};
         e.moff = m_first;
         return launch_op<T, decltype(C)>(la, lb, e, M, N, cdiv(D, KT<T>::BK), tail, st);

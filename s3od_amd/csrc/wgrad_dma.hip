@@ -4,6 +4,7 @@
 // AGPRs and the 256 VGPRs hold the fragment bases, the DMA offsets and the operand fragments -- in the VGPR form
 // the same loop spilled 44 VGPRs and ran ~140 VALU (AGPR copies) per 576 MFMAs, ~50 without.
 #include "gemm.hpp"
+#include "conv_kernels.hpp"
 #include <type_traits>
 #include <utility>
 

@@ -1,8 +1,11 @@
-"""Per-kernel gfx950 ISA comparison of one HIP source between two git revisions, or a revision and the work tree
+"""Per-kernel gfx950 ISA comparison of HIP sources between two git revisions, or a revision and the work tree
 (dev tool, CPU only): one line per kernel, identical / DIFFERENT, with the compiler's resource figures for both.
 
     python tools/isa_diff.py s3od_amd/csrc/attention.hip HEAD            # HEAD against the work tree
     python tools/isa_diff.py s3od_amd/csrc/attention.hip HEAD~2 HEAD
+    python tools/isa_diff.py s3od_amd/csrc/conv_ops.hip s3od_amd/csrc/linear_ops.hip HEAD     # several sources, one run
+
+The exit status is 1 when any kernel is DIFFERENT or has no partner on the other side; --allow-different makes it 0.
 
 Each side's csrc/ is compiled with the flags the Makefile gives that file.  The texts compared are the kernel bodies
 without comments, debug and section directives and blank lines, with the kernel's own mangled name and the per-file function
@@ -55,9 +58,9 @@ def compile_rev(src, rev, tmp):
     return out
 
 
-def main():
-    src = Path(sys.argv[1])
-    revs = (sys.argv[2:] + [None])[:2]
+def diff_source(src, revs):
+    """prints the report of one source -> the number of kernels that are DIFFERENT or unpaired"""
+    bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         a, b = (compile_rev(src, r, tmp) for r in revs)
     print(f"# {src}: {revs[0] or 'work tree'} -> {revs[1] or 'work tree'}")
@@ -73,9 +76,20 @@ def main():
     for n in sorted(set(a) | set(b), key=short):
         if n not in a or n not in b:
             print(f"{'only in ' + str(revs[n in b] or 'work tree'):18s} {short(n)}: {fig((a.get(n) or b.get(n))[1])}")
+            bad += 1
             continue
         same = a[n][0] == b[n][0]
+        bad += not same
         print(f"{'identical' if same else 'DIFFERENT':18s} {short(n)}: {fig(a[n][1])}" + ("" if a[n][1] == b[n][1] and same else f" -> {fig(b[n][1])}"))
+    return bad
+
+
+def main():
+    args = [a for a in sys.argv[1:] if a != "--allow-different"]
+    srcs = [Path(a) for a in args if a.endswith(".hip")]
+    revs = ([a for a in args if not a.endswith(".hip")] + [None])[:2]
+    bad = sum([diff_source(src, revs) for src in srcs])
+    sys.exit(1 if bad and "--allow-different" not in sys.argv else 0)
 
 
 if __name__ == "__main__":
