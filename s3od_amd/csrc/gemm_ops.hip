@@ -1,8 +1,12 @@
-// Hand-pipelined conv kernels with counted vmcnt waits: the register-weight 3x3 / ConvTranspose / strided convs, the
-// register-staged halo weight gradient and the 4x4 s2 LDS-DMA weight gradient, with their launchers and shape
-// predicates (declared in conv_kernels.hpp; the entries that route to them are in conv_ops.hip).
-#include "gemm.hpp"
-#include "conv_kernels.hpp"
+// Hand-pipelined conv kernels with counted vmcnt waits (their shared parts are in conv_rw.hpp):
+//   conv3x3_c64_rw_kernel      register-weight 3x3 s1 convs: forward (+ ReLU), ReLU'-masked data gradient, mask heads
+//   convT4s2_rw_kernel         register-weight ConvTranspose2d(128, 64, 4, s2, p1), sub-pixel forward
+//   conv4s2_rw_kernel          its data gradient, the strided Conv2d(64, 128, 4, s2, p1)
+//   conv3x3_wgrad_halo_kernel  register-staged halo-tile 3x3 weight gradient
+//   conv4s2_wgrad_dma_kernel   LDS-DMA weight gradient of the 4x4 s2 conv view
+// with their launchers and shape predicates (declared in conv_kernels.hpp; the entries that route to them are in
+// conv_ops.hip).
+#include "conv_rw.hpp"
 
 // ---------------------------------------------------------------- register-weight 3x3 conv, 64 -> 64
 // The full-resolution 64-channel convs (upsample_2x.2 forward and its stride-1 data gradient) move
@@ -20,7 +24,8 @@
 // Input channels CI = 64 (tile 8 x 32) or 96 (the mask heads' data gradient: tile 8 x 16, 192-B halo rows).
 template <int CI> struct RwShape {
   static constexpr int TH = 8, TW = CI == 64 ? 32 : 16, HC = TW + 2, PX = (TH + 2) * HC;   // halo pixels
-  static constexpr int ROWB = CI * 2, KK = CI / 32, NPC = TW / 16, PB = 4 * NPC;          // 16-px blocks per wave
+  static constexpr int ROWB = CI * 2, CHUNKS = CI / 8, GPIX = ROWB;                       // LDS row = global pixel
+  static constexpr int KK = CI / 32, NPC = TW / 16, PB = 4 * NPC;                         // 16-px blocks per wave
   static constexpr int PIECES = ((PX * ROWB + 4095) / 4096) * 4, PPW = PIECES / 4;        // 1 KiB DMA pieces
   static constexpr int BUF = PIECES * 1024, LDS = 3 * BUF + 2048;       // + bias / column sums / head partials
   static_assert(LDS <= 160 * 1024, "register-weight conv LDS budget");
@@ -36,17 +41,17 @@ template <int CI> struct RwShape {
 // MODE 3: the 3 mask heads (src/s3od/model.py:440-452,461-467): 96 output channels (48 per wave, NB = 3),
 //   h = ReLU(acc + b1) -> hsave (bf16 [px][96]) and logit_k = b2[k] + h[32k .. 32k+31] . w2[k] -> logits [B][3][H][W];
 //   head 1 straddles the two waves of a row group: the odd wave's part goes through LDS (one extra barrier)
-// Every wave issues a FIXED sequence of vector-memory instructions per tile (PPW DMA pieces, PB mask loads, PB stores:
+// Every wave issues a FIXED sequence of vector-memory instructions per tile (PB mask loads, PPW DMA pieces, PB stores:
 // dummy pieces / out-of-image lanes use an out-of-range buffer offset instead of a branch), so the counted vmcnt
-// that retires a tile's halo is a per-phase constant.
-// GB > 0 (MODE 0 / 2; mode 1 is launched ungrouped, see launch_rw): the tile's PB blocks run in groups of GB (all 9 * KK steps of one group's GB x NB accumulators,
-// then the next group's), and each group's epilogue (ReLU / mask, lane-pair trade, pack, store) is issued between the
+// that retires a tile's halo is a per-phase constant (ring_wait).
+// The tile's PB blocks run in groups (all 9 * KK steps of one group's accumulators, then the next group's).
+// GB = 0 (mode 1, see conv3x3_rw_dgrad_launch, and mode 3): one group of PB blocks, its epilogue at once.
+// GB > 0 (MODE 0 / 2): groups of GB blocks, and each group's epilogue (ReLU, lane-pair trade, pack, store) is issued between the
 // NEXT group's MFMAs -- the last group's carried into the next tile's first group (a dummy group with out-of-range
 // stores before the first tile) -- so with one wave per SIMD the matrix pipe no longer idles through the epilogue.
 // Same MFMA chain per accumulator (outputs bit-identical to GB = 0); per tile still PB stores after the halo issue,
 // so the counted waits are unchanged.
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <int MODE, int CI, int GB>
 __global__ void __launch_bounds__(256, 1) conv3x3_c64_rw_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
                                                                  const float* __restrict__ bias,
@@ -58,15 +63,12 @@ __global__ void __launch_bounds__(256, 1) conv3x3_c64_rw_kernel(const bf16* __re
   constexpr int PB = S::PB, PPW = S::PPW, NPC = S::NPC, HC = S::HC, ROWB = S::ROWB;
   constexpr int NB = MODE == 3 ? 3 : 2, CO = 32 * NB;     // 16-channel blocks per wave / output channels
   static_assert(MODE != 3 || (CI == 64 && NPC == 2), "mask heads: 64 input channels, 8 x 32 tiles");
-  static_assert(GB == 0 || (MODE != 3 && PB % GB == 0), "grouped epilogue: whole groups (the mask heads run ungrouped)");
+  static_assert(GB == 0 || ((MODE == 0 || MODE == 2) && PB % GB == 0), "grouped epilogue: whole groups, forward only");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int lr = lane & 15, lg = lane >> 4, odd = lg & 1;
   const int row0 = 4 * (wave >> 1), ch0 = 16 * NB * (wave & 1);   // this wave's output rows / channels
-  // tiles: XCD x = blockIdx % 8 owns the contiguous range [x*n/8, (x+1)*n/8) (neighbouring tiles share halo
-  // rows in that XCD's L2); its workgroups stride through it
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, wpx = (nwg + 7 - xcd) >> 3, wi = blockIdx.x >> 3;
-  const int t_beg = (int)((long)ntiles * xcd / 8), t_end = (int)((long)ntiles * (xcd + 1) / 8);
+  const PersistentTiles pt(ntiles);
   const long img_i = (long)H * W * CI, img_o = (long)H * W * CO;    // elements per image
 
   // weights -> registers: lane (lr, lg) holds w[co = ch0 + 16 nb + lr][tap][ci = 32 kk + 8 lg .. +7]
@@ -79,27 +81,11 @@ __global__ void __launch_bounds__(256, 1) conv3x3_c64_rw_kernel(const bf16* __re
       for (int nb = 0; nb < NB; nb++)
         wr[tap][kk][nb] = *(const bf16x8*)(w + ((long)(ch0 + nb * 16 + lr) * 9 + tap) * CI + kk * 32 + lg * 8);
 
-  // DMA lane constants: piece p = PPW wave + i covers LDS bytes [1024 p, 1024 p + 1024) of a ring slot, laid out
-  // [px][16-B slot]; lane writes bytes 16 lane .. +15 of the piece = logical chunk slot^-1 of pixel px
-  int dm[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const int b = (wave * PPW + i) * 1024 + lane * 16, px = b / ROWB, ch = S::slot((b % ROWB) >> 4, px);
-    dm[i] = px < S::PX ? ((px / HC) << 16) | ((px % HC) << 4) | ch : -1;
-  }
-  auto issue = [&](int tile, int slot) {            // tile >= t_end: dummy pieces (zeros into a free slot)
-    const bool live = tile < t_end;
-    const int tc = live ? tile : t_beg;
-    const int txi = tc % tiles_x, t2 = tc / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const int ty0 = tyi * S::TH - 1, tx0 = txi * S::TW - 1;
-    const auto r = make_rsrc(x + bb * img_i, (unsigned long)img_i * 2);
-    char* dst = smem + slot * S::BUF + wave * PPW * 1024;
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      const int v = dm[i], gy = ty0 + (v >> 16), gx = tx0 + ((v >> 4) & 0xfff);
-      const bool ok = live && v >= 0 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-      blds16(r, ok ? (unsigned)((gy * W + gx) * ROWB + (v & 15) * 16) : 0x80000000u, dst + i * 1024);
-    }
+  const HaloRing<S> ring(smem, wave, lane);
+  auto issue = [&](int tile, int slot) {            // tile >= pt.end: dummy pieces (zeros into a free slot)
+    const bool live = tile < pt.end;
+    const TileAt t = tile_at(live ? tile : pt.beg, tiles_x, tiles_y);
+    ring.issue(make_rsrc(x + t.bb * img_i, (unsigned long)img_i * 2), t.tyi * S::TH - 1, t.txi * S::TW - 1, H, W, live, slot);
   };
   // halo fragment addresses: px = L + off (L = row0 * HC + lr per lane, off compile-time per (block, tap)); the
   // slot term depends on the lane and on off & 7 only, so yb[off & 7][kk] + ROWB * off = per-lane base + immediate
@@ -124,250 +110,157 @@ __global__ void __launch_bounds__(256, 1) conv3x3_c64_rw_kernel(const bf16* __re
   __syncthreads();
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-  // GB > 0: the carried group (accumulators, store offsets, masks, output descriptor); a dummy before the first tile
+  // GB > 0: the carried group (accumulators, store offsets, batch index); a dummy before the first tile
   constexpr int GBC = GB > 0 ? GB : 1;
   f32x4 cacc[GBC][NB];
   unsigned cpo[GBC];
-  u32x4v crm[GBC];
 #pragma unroll
   for (int q = 0; q < GBC; q++) {
     cpo[q] = 0x80000000u;
-    crm[q] = u32x4v{0u, 0u, 0u, 0u};
 #pragma unroll
     for (int nb = 0; nb < NB; nb++) cacc[q][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   int cbb = 0;                                        // batch index of the carried group's tile
-  // epilogue of one 16-px block: lane holds out[px = block, lr][co = ch0 + 16 nb + 4 lg .. +3]; v_permlane16_swap
-  // trades rows 1 / 3 of the first operand with rows 0 / 2 of the second (row = 16 lanes = one lg): the even lg keeps
-  // its nb 0 and receives the odd partner's nb 0, the odd lg keeps nb 1 and receives the even's -> channels cb .. cb+7
+  // epilogue of one 16-px block (trade_store8; mode 1: the ReLU' mask, out-of-image lanes read 0, and the column sums)
   // (the output descriptor is built here from the batch index: in a round-5 build a descriptor carried across tiles
   // in SGPRs lost its range word in the grouped mode-1 instance, whose in-tile group stores were dropped)
-  auto epi_blk = [&](const f32x4 (&a)[NB], unsigned p, u32x4v mraw, int bbx) {
+  auto epi_blk = [&](const f32x4 (&a)[NB], unsigned p, int bbx, u32x4 mraw = u32x4{0u, 0u, 0u, 0u}) {
     const auto r = make_rsrc(out + bbx * img_o, out ? (unsigned long)img_o * 2 : 0ul);
-    float o[8];
+    trade_store8<MODE == 2>(a[0], a[1], r, p, [&](float (&o)[8]) {
+      if constexpr (MODE == 1) {
+        const bf16x8 m = __builtin_bit_cast(bf16x8, mraw);
 #pragma unroll
-    for (int e = 0; e < 4; e++) {
-      float v0 = a[0][e], v1 = a[1][e];
-      if (MODE == 2) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-      const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
-      o[e] = __uint_as_float(sw[0]);               // channels cb + 0..3
-      o[4 + e] = __uint_as_float(sw[1]);           // channels cb + 4..7
-    }
-    if constexpr (MODE == 1) {
-      const bf16x8 m = __builtin_bit_cast(bf16x8, mraw);
+        for (int e = 0; e < 8; e++) o[e] = (float)m[e] > 0.f ? o[e] : 0.f;
 #pragma unroll
-      for (int e = 0; e < 8; e++) o[e] = (float)m[e] > 0.f ? o[e] : 0.f;   // out-of-image lanes: mask reads 0
-#pragma unroll
-      for (int e = 0; e < 8; e++) cs[e] += o[e];     // column sums of channels cb .. cb+7 (lane partials)
-    }
-    bf16x8 ob;
-#pragma unroll
-    for (int e = 0; e < 8; e++) ob[e] = (bf16)o[e];
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, ob), r, p, 0, 0);
+        for (int e = 0; e < 8; e++) cs[e] += o[e];
+      }
+    });
   };
 
-  int tile = t_beg + wi, k = 0;
-  issue(tile, 0);
-  issue(tile + wpx, 1);
-  for (; tile < t_end; tile += wpx, k++) {
-    const int txi = tile % tiles_x, t2 = tile / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const auto ro = make_rsrc(out + bb * img_o, out ? (unsigned long)img_o * 2 : 0ul);   // MODE 3: hsave is optional
+  int k = 0;
+  issue(pt.first, 0);
+  issue(pt.first + pt.stride, 1);
+  for (int tile = pt.first; tile < pt.end; tile += pt.stride, k++) {
+    const TileAt t = tile_at(tile, tiles_x, tiles_y);
     unsigned po[PB];                                  // byte offset of this lane's 8-channel run per 16-px block (or OOB)
 #pragma unroll
     for (int pb = 0; pb < PB; pb++) {
-      const int gy = tyi * S::TH + row0 + pb / NPC, gx = txi * S::TW + (pb % NPC) * 16 + lr;
+      const int gy = t.tyi * S::TH + row0 + pb / NPC, gx = t.txi * S::TW + (pb % NPC) * 16 + lr;
       po[pb] = (gy < H && gx < W) ? (unsigned)((gy * W + gx) * (CO * 2) + cb * 2) : 0x80000000u;
     }
     // data-gradient mask runs of this tile, issued before the next halo's DMA (their wait leaves it in flight)
-    u32x4v rm_[PB];
+    u32x4 rm_[PB];
     if constexpr (MODE == 1) {
-      const auto rr = make_rsrc(res1 + bb * img_o, (unsigned long)img_o * 2);
+      const auto rr = make_rsrc(res1 + t.bb * img_o, (unsigned long)img_o * 2);
 #pragma unroll
       for (int pb = 0; pb < PB; pb++) rm_[pb] = __builtin_amdgcn_raw_buffer_load_b128(rr, po[pb], 0, 0);
     }
-    // retire this tile's halo (own pieces): the vector-memory ops issued after them are a per-phase constant
-    //   k = 0: next halo [+ masks];  k = 1: [masks,] halo, stores [, masks];  k >= 2: stores [, masks], halo, stores [, masks]
-    //   (MODE 3 stores 2 PB hsave runs + 8 logit rows = 3 PB per tile)
-    constexpr int NS = MODE == 3 ? 3 * PB : PB;       // stores per tile
-    if (k == 0) { if constexpr (MODE == 1) wait_vmcnt<PPW + PB>(); else wait_vmcnt<PPW>(); }
-    else if (k == 1) { if constexpr (MODE == 1) wait_vmcnt<PB + PPW + PB + PB>(); else wait_vmcnt<PPW + NS>(); }
-    else { if constexpr (MODE == 1) wait_vmcnt<PB + PB + PPW + PB + PB>(); else wait_vmcnt<NS + PPW + NS>(); }
-    __builtin_amdgcn_s_barrier();                    // every wave's pieces landed; every wave done with slot k-1
-    asm volatile("" ::: "memory");
-    issue(tile + 2 * wpx, (k + 2) % 3);
+    // stores per tile: PB, or (MODE 3) 2 PB hsave runs + 8 logit rows = 3 PB; mask loads: PB (MODE 1)
+    ring_wait<PPW, MODE == 3 ? 3 * PB : PB, MODE == 1 ? PB : 0>(k);
+    issue(tile + 2 * pt.stride, (k + 2) % 3);
     const char* hb = smem + (k % 3) * S::BUF;
-    constexpr int NST = 9 * S::KK;
-    if constexpr (GB > 0) {
-      // fragments of group gi's GB blocks for step st; the group's MFMAs; the carried group's epilogue in the first
-      // GB step pairs
-      auto rd_g = [&](int gi, int st, bf16x8 (&fa)[GB]) {
+    constexpr int G = GB > 0 ? GB : PB;               // blocks per group
+#pragma unroll
+    for (int gi = 0; gi < PB / G; gi++) {
+      f32x4 acc[G][NB];                               // acc[q][nb]: D[co = ch0 + 16 nb + 4 lg + e][px = block gi G + q, lr]
+#pragma unroll
+      for (int nb = 0; nb < NB; nb++) {
+        const f32x4 b0 = MODE != 1 ? *(const f32x4*)(aux + ch0 + nb * 16 + 4 * lg) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int q = 0; q < G; q++) acc[q][nb] = b0;
+      }
+      // 9 * KK (tap, k-chunk) steps of G x NB MFMAs on the group's G halo fragments; the carried group's epilogue in
+      // the first GB step pairs
+      auto rd = [&](int st, bf16x8 (&fa)[G]) {
         const int tap = st / S::KK, kk = st % S::KK, dy = tap / 3, dx = tap - 3 * (tap / 3);
 #pragma unroll
-        for (int q = 0; q < GB; q++) {
-          const int pb = gi * GB + q, off = (pb / NPC + dy) * HC + (pb % NPC) * 16 + dx;
+        for (int q = 0; q < G; q++) {
+          const int pb = gi * G + q, off = (pb / NPC + dy) * HC + (pb % NPC) * 16 + dx;
           fa[q] = *(const bf16x8*)(hb + yb[off & 7][kk] + off * ROWB);
         }
       };
+      auto mm = [&](int st, const bf16x8 (&fa)[G]) {
 #pragma unroll
-      for (int gi = 0; gi < PB / GB; gi++) {
-        f32x4 acc[GB][NB];
+        for (int q = 0; q < G; q++)
 #pragma unroll
-        for (int nb = 0; nb < NB; nb++) {
-          const f32x4 b0 = MODE != 1 ? *(const f32x4*)(aux + ch0 + nb * 16 + 4 * lg) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int q = 0; q < GB; q++) acc[q][nb] = b0;
-        }
-        auto mm_g = [&](int st, const bf16x8 (&fa)[GB]) {
-#pragma unroll
-          for (int q = 0; q < GB; q++)
-#pragma unroll
-            for (int nb = 0; nb < NB; nb++)
-              acc[q][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[st / S::KK][st % S::KK][nb], fa[q], acc[q][nb], 0, 0, 0);
-        };
-        bf16x8 fa0[GB], fa1[GB];
-        rd_g(gi, 0, fa0);
-#pragma unroll
-        for (int st = 0; st < NST; st += 2) {
-          if (st + 1 < NST) rd_g(gi, st + 1, fa1);
-          __builtin_amdgcn_sched_barrier(0);
-          mm_g(st, fa0);
-          if (st / 2 < GB) epi_blk(cacc[st / 2], cpo[st / 2], crm[st / 2], cbb);
-          __builtin_amdgcn_sched_barrier(0);
-          if (st + 2 < NST) rd_g(gi, st + 2, fa0);
-          __builtin_amdgcn_sched_barrier(0);
-          if (st + 1 < NST) mm_g(st + 1, fa1);
-          __builtin_amdgcn_sched_barrier(0);
-        }
+          for (int nb = 0; nb < NB; nb++)
+            acc[q][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[st / S::KK][st % S::KK][nb], fa[q], acc[q][nb], 0, 0, 0);
+      };
+      rw_steps<9 * S::KK, G>(rd, mm, [&](int pair) {
+        if constexpr (GB > 0) { if (pair < GB) epi_blk(cacc[pair], cpo[pair], cbb); }
+      });
+      if constexpr (GB > 0) {
 #pragma unroll
         for (int q = 0; q < GB; q++) {
 #pragma unroll
           for (int nb = 0; nb < NB; nb++) cacc[q][nb] = acc[q][nb];
           cpo[q] = po[gi * GB + q];
-          if constexpr (MODE == 1) crm[q] = rm_[gi * GB + q];
         }
-        cbb = bb;
-      }
-      continue;
-    }
-    f32x4 acc[PB][NB];                                // acc[pb][nb]: D[co = ch0 + 16 nb + 4 lg + e][px = block pb, lr]
+        cbb = t.bb;
+      } else if constexpr (MODE == 3) {
+        const auto ro = make_rsrc(out + t.bb * img_o, out ? (unsigned long)img_o * 2 : 0ul);   // hsave is optional
+        // h = ReLU(acc) (b1 was the initial value); hsave: channels cb .. cb+7 (nb 0 / 1, trade_store8) and
+        // ch0 + 32 + 4 lg .. +3 (nb 2); head partials: per 16-channel block, summed over the 4 lg lanes
+        float hp[PB][3];
 #pragma unroll
-    for (int nb = 0; nb < NB; nb++) {
-      const f32x4 b0 = MODE != 1 ? *(const f32x4*)(aux + ch0 + nb * 16 + 4 * lg) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int pb = 0; pb < PB; pb++) {
+          float v[3][4];
 #pragma unroll
-      for (int pb = 0; pb < PB; pb++) acc[pb][nb] = b0;
-    }
-    // 9 * KK (tap, k-chunk) steps of 2 PB MFMAs; the next step's PB halo fragments are read before this step's MFMAs
-    auto rd = [&](int st, bf16x8 (&fa)[PB]) {
-      const int tap = st / S::KK, kk = st % S::KK, dy = tap / 3, dx = tap - 3 * (tap / 3);
+          for (int nb = 0; nb < 3; nb++)
 #pragma unroll
-      for (int pb = 0; pb < PB; pb++) {
-        const int off = (pb / NPC + dy) * HC + (pb % NPC) * 16 + dx;
-        fa[pb] = *(const bf16x8*)(hb + yb[off & 7][kk] + off * ROWB);
-      }
-    };
-    auto mm = [&](int st, const bf16x8 (&fa)[PB]) {
+            for (int e = 0; e < 4; e++) v[nb][e] = fmaxf(acc[pb][nb][e], 0.f);
+          trade_store8<true>(acc[pb][0], acc[pb][1], ro, po[pb]);
+          const unsigned p2 = po[pb] == 0x80000000u ? po[pb] : po[pb] - cb * 2 + (ch0 + 32 + 4 * lg) * 2;
+          const bf16x4 o2 = {(bf16)v[2][0], (bf16)v[2][1], (bf16)v[2][2], (bf16)v[2][3]};
+          __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o2), ro, p2, 0, 0);
 #pragma unroll
-      for (int pb = 0; pb < PB; pb++)
+          for (int nb = 0; nb < 3; nb++) {
+            float d = 0.f;
 #pragma unroll
-        for (int nb = 0; nb < NB; nb++)
-          acc[pb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[st / S::KK][st % S::KK][nb], fa[pb], acc[pb][nb], 0, 0, 0);
-    };
-    bf16x8 fa0[PB], fa1[PB];
-    rd(0, fa0);
-#pragma unroll
-    for (int st = 0; st < NST; st += 2) {
-      if (st + 1 < NST) rd(st + 1, fa1);
-      __builtin_amdgcn_sched_barrier(0);
-      mm(st, fa0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (st + 2 < NST) rd(st + 2, fa0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (st + 1 < NST) mm(st + 1, fa1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (MODE == 3) {
-      // h = ReLU(acc) (b1 was the initial value); hsave: channels cb .. cb+7 (nb 0 / 1 traded as below) and
-      // ch0 + 32 + 4 lg .. +3 (nb 2); head partials: per 16-channel block, summed over the 4 lg lanes
-      float hp[PB][3];
-#pragma unroll
-      for (int pb = 0; pb < PB; pb++) {
-        float v[3][4];
-#pragma unroll
-        for (int nb = 0; nb < 3; nb++)
-#pragma unroll
-          for (int e = 0; e < 4; e++) v[nb][e] = fmaxf(acc[pb][nb][e], 0.f);
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[0][e]), __float_as_uint(v[1][e]), false, false);
-          o[e] = __uint_as_float(sw[0]);
-          o[4 + e] = __uint_as_float(sw[1]);
+            for (int e = 0; e < 4; e++) d += v[nb][e] * aux[96 + ch0 + 16 * nb + 4 * lg + e];
+            d += __shfl_xor(d, 16);
+            d += __shfl_xor(d, 32);
+            hp[pb][nb] = d;
+          }
         }
-        bf16x8 ob;
+        // wave half 0 (channels 0-47): head 0 = blocks 0 + 1, head 1 = block 2 + the odd wave's block 0;
+        // half 1 (48-95): head 2 = blocks 1 + 2
+        float* part = aux + 256 + (row0 + 0) * 32;
+        if (wave & 1) {
 #pragma unroll
-        for (int e = 0; e < 8; e++) ob[e] = (bf16)o[e];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, ob), ro, po[pb], 0, 0);
-        const unsigned p2 = po[pb] == 0x80000000u ? po[pb] : po[pb] - cb * 2 + (ch0 + 32 + 4 * lg) * 2;
-        const bf16x4 o2 = {(bf16)v[2][0], (bf16)v[2][1], (bf16)v[2][2], (bf16)v[2][3]};
-        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, o2), ro, p2, 0, 0);
-#pragma unroll
-        for (int nb = 0; nb < 3; nb++) {
-          float d = 0.f;
-#pragma unroll
-          for (int e = 0; e < 4; e++) d += v[nb][e] * aux[96 + ch0 + 16 * nb + 4 * lg + e];
-          d += __shfl_xor(d, 16);
-          d += __shfl_xor(d, 32);
-          hp[pb][nb] = d;
+          for (int pb = 0; pb < PB; pb++)
+            if (lg == 0) part[(pb / NPC) * 32 + (pb % NPC) * 16 + lr] = hp[pb][0];
         }
-      }
-      // wave half 0 (channels 0-47): head 0 = blocks 0 + 1, head 1 = block 2 + the odd wave's block 0;
-      // half 1 (48-95): head 2 = blocks 1 + 2
-      float* part = aux + 256 + (row0 + 0) * 32;
-      if (wave & 1) {
+        lds_barrier();
+        const auto rl = make_rsrc(logits + (long)t.bb * 3 * H * W, (unsigned long)3 * H * W * 4);
 #pragma unroll
-        for (int pb = 0; pb < PB; pb++)
-          if (lg == 0) part[(pb / NPC) * 32 + (pb % NPC) * 16 + lr] = hp[pb][0];
-      }
-      lds_barrier();
-      const auto rl = make_rsrc(logits + (long)bb * 3 * H * W, (unsigned long)3 * H * W * 4);
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        // lanes lg 0 / 1 store the row's two 16-pixel blocks (64 + 64 contiguous bytes); lg 2 / 3 are out of range
-        const int gy = tyi * S::TH + row0 + r, gx = txi * S::TW + (lg & 1) * 16 + lr;
-        const bool ok = lg < 2 && gy < H && gx < W;
-        const int pb = 2 * r + (lg & 1);
-        const unsigned base = (unsigned)(gy * W + gx) * 4;
-        if (!(wave & 1)) {
-          const float l0 = aux[192] + hp[2 * r][0] + hp[2 * r][1], l0b = aux[192] + hp[2 * r + 1][0] + hp[2 * r + 1][1];
-          const float l1 = aux[193] + hp[2 * r][2] + part[r * 32 + lr], l1b = aux[193] + hp[2 * r + 1][2] + part[r * 32 + 16 + lr];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l0b : l0), rl, ok ? base : 0x80000000u, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l1b : l1), rl, ok ? base + (unsigned)H * W * 4 : 0x80000000u, 0, 0);
-        } else {
-          const float l2 = aux[194] + hp[2 * r][1] + hp[2 * r][2], l2b = aux[194] + hp[2 * r + 1][1] + hp[2 * r + 1][2];
-          __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l2b : l2), rl, ok ? base + 2u * H * W * 4 : 0x80000000u, 0, 0);
-          __builtin_amdgcn_raw_buffer_store_b32(0u, rl, 0x80000000u, 0, 0);   // keeps the per-tile store count uniform
+        for (int r = 0; r < 4; r++) {
+          // lanes lg 0 / 1 store the row's two 16-pixel blocks (64 + 64 contiguous bytes); lg 2 / 3 are out of range
+          const int gy = t.tyi * S::TH + row0 + r, gx = t.txi * S::TW + (lg & 1) * 16 + lr;
+          const bool ok = lg < 2 && gy < H && gx < W;
+          const unsigned base = (unsigned)(gy * W + gx) * 4;
+          if (!(wave & 1)) {
+            const float l0 = aux[192] + hp[2 * r][0] + hp[2 * r][1], l0b = aux[192] + hp[2 * r + 1][0] + hp[2 * r + 1][1];
+            const float l1 = aux[193] + hp[2 * r][2] + part[r * 32 + lr], l1b = aux[193] + hp[2 * r + 1][2] + part[r * 32 + 16 + lr];
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l0b : l0), rl, ok ? base : 0x80000000u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l1b : l1), rl, ok ? base + (unsigned)H * W * 4 : 0x80000000u, 0, 0);
+          } else {
+            const float l2 = aux[194] + hp[2 * r][1] + hp[2 * r][2], l2b = aux[194] + hp[2 * r + 1][1] + hp[2 * r + 1][2];
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint((lg & 1) ? l2b : l2), rl, ok ? base + 2u * H * W * 4 : 0x80000000u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(0u, rl, 0x80000000u, 0, 0);   // keeps the per-tile store count uniform
+          }
         }
-        (void)pb;
-      }
-    } else {
+      } else {
 #pragma unroll
-      for (int pb = 0; pb < PB; pb++) epi_blk(acc[pb], po[pb], rm_[pb], bb);
+        for (int pb = 0; pb < PB; pb++) epi_blk(acc[pb], po[pb], t.bb, rm_[pb]);
+      }
     }
   }
   if constexpr (GB > 0) {                             // the last tile's carried group
 #pragma unroll
-    for (int q = 0; q < GB; q++) epi_blk(cacc[q], cpo[q], crm[q], cbb);
+    for (int q = 0; q < GB; q++) epi_blk(cacc[q], cpo[q], cbb);
   }
-  if (MODE == 1 && colsum) {                          // 16 lanes (lr) -> 1, LDS atomics, one global add per channel
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float c = cs[e];
-      c += __shfl_xor(c, 1); c += __shfl_xor(c, 2); c += __shfl_xor(c, 4); c += __shfl_xor(c, 8);
-      if (lr == 0) atomicAdd(aux + cb + e, c);
-    }
-    __syncthreads();
-    if (tid < 64) atomicAdd(colsum + tid, aux[tid]);
-  }
+  if (MODE == 1 && colsum) flush_colsum<64>(cs, aux, colsum, cb);
   wait_vmcnt<0>();        // no LDS-DMA (dummy pieces included) may still be landing when the workgroup retires
 }
 
@@ -379,16 +272,11 @@ template <int MODE, int CI, int GB>
 static int launch_rw_g(const bf16* x, const bf16* w, const float* bias, const bf16* res1, float* colsum, bf16* out,
                        int B, int H, int W, hipStream_t st, const float* w2, const float* b2, float* logits) {
   typedef RwShape<CI> S;
-  auto kfn = conv3x3_c64_rw_kernel<MODE, CI, GB>;
-  static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS), true);   // once per process (thread-safe static init)
-  (void)attr;
   const int tx = cdiv(W, S::TW), ty = cdiv(H, S::TH);
   const long tiles = (long)B * tx * ty;
-  if (tiles >= (1L << 31)) { s3od_set_error("conv rw: too many tiles"); return 22; }
-  const int nwg = (int)std::min<long>(std::max<long>(tiles, 8), (long)s3od_cu_count());   // one persistent WG per CU, >= 8 so every XCD owns its range
-  hipLaunchKernelGGL(kfn, dim3(nwg), dim3(256), S::LDS, st, x, w, bias, res1, colsum, out, H, W, tx, ty, (int)tiles, w2, b2,
-                     logits);
-  return s3od_check_launch("conv3x3_c64_rw");
+  return launch_tiled<conv3x3_c64_rw_kernel<MODE, CI, GB>, S::LDS, 256>(
+      "conv3x3_c64_rw", "conv rw: too many tiles", tiles, grid_xcd(tiles), st, x, w, bias, res1, colsum, out, H, W, tx, ty,
+      (int)tiles, w2, b2, logits);
 }
 // modes 0 / 2 (forward): the grouped epilogue (S3OD_RW_GB = blocks per group: 2 default, or 0 = the epilogue after all
 // MFMAs).  Measured (tools/conv64_bench.py, bs 16 x 1024^2 64 -> 64 + ReLU, same box): GB 0 1290-1309 us, GB 2 1225-1242,
@@ -427,23 +315,24 @@ int mask_heads_rw_launch(const bf16* feat, const bf16* w1p, const float* b1, con
 //     2 classes x 4 taps x 128 x 32 weights sit in registers as MFMA A fragments (256 VGPRs, gathered once);
 //   * epilogue as in the 3x3 kernel: bias is the accumulators' initial value, ReLU, lane-pair channel trade,
 //     one 16-B store per lane per 16-pixel block (stride-2 output columns; the other parity's wave fills the gaps).
-namespace ct {
-constexpr int TH = 8, TW = 16, HC = TW + 2, PX = (TH + 2) * HC, ROWB = 288;          // 18 slots of 16 B per pixel
-constexpr int PIECES = ((PX * ROWB + 4095) / 4096) * 4, PPW = PIECES / 4, BUF = PIECES * 1024, LDS = 3 * BUF + 1024;
-static_assert(LDS <= 160 * 1024, "convT LDS budget");
-}  // namespace ct
+struct CtShape {
+  static constexpr int TH = 8, TW = 16, HC = TW + 2, PX = (TH + 2) * HC;
+  static constexpr int ROWB = 288, CHUNKS = 16, GPIX = 256;                           // 18 slots of 16 B per pixel
+  static constexpr int PIECES = ((PX * ROWB + 4095) / 4096) * 4, PPW = PIECES / 4, BUF = PIECES * 1024, LDS = 3 * BUF + 1024;
+  static_assert(LDS <= 160 * 1024, "convT LDS budget");
+  DEV static int slot(int c, int) { return c; }
+};
 template <bool RELU>
 __global__ void __launch_bounds__(256, 1) convT4s2_rw_kernel(const bf16* __restrict__ x, const bf16* __restrict__ wt,
                                                               const float* __restrict__ bias, bf16* __restrict__ out,
                                                               int H, int W, int tiles_x, int tiles_y, int ntiles) {
-  using namespace ct;
-  constexpr int NS = 16;                                            // stores per tile per wave (2 classes x 8 rows)
+  typedef CtShape S;
+  constexpr int HC = S::HC, ROWB = S::ROWB;
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int lr = lane & 15, lg = lane >> 4, odd = lg & 1;
   const int py = wave >> 1, ch0 = 32 * (wave & 1);
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, wpx = (nwg + 7 - xcd) >> 3, wi = blockIdx.x >> 3;
-  const int t_beg = (int)((long)ntiles * xcd / 8), t_end = (int)((long)ntiles * (xcd + 1) / 8);
+  const PersistentTiles pt(ntiles);
   const long img_i = (long)H * W * 128, img_o = (long)4 * H * W * 64;
 
   // weights: wt = [co = 64][ky][kx][ci = 128] (ConvTranspose2d weight [128][64][4][4] transposed, s3od_repack_multi
@@ -458,46 +347,28 @@ __global__ void __launch_bounds__(256, 1) convT4s2_rw_kernel(const bf16* __restr
         const int a = s >> 3, c = (s >> 2) & 1, kk = s & 3, ky = 1 - py + 2 * a, kx = 1 - pxc + 2 * c;
         wr[pxc][s][nb] = *(const bf16x8*)(wt + ((ch0 + nb * 16 + lr) * 16 + ky * 4 + kx) * 128 + kk * 32 + lg * 8);
       }
-  int dm[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const int b = (wave * PPW + i) * 1024 + lane * 16, px = b / ROWB, ch = (b % ROWB) >> 4;
-    dm[i] = (px < PX && ch < 16) ? ((px / HC) << 16) | ((px % HC) << 4) | ch : -1;
-  }
+  const HaloRing<S> ring(smem, wave, lane);
   auto issue = [&](int tile, int slot) {
-    const bool live = tile < t_end;
-    const int tc = live ? tile : t_beg;
-    const int txi = tc % tiles_x, t2 = tc / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const int ty0 = tyi * TH - 1, tx0 = txi * TW - 1;
-    const auto r = make_rsrc(x + bb * img_i, (unsigned long)img_i * 2);
-    char* dst = smem + slot * BUF + wave * PPW * 1024;
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      const int v = dm[i], gy = ty0 + (v >> 16), gx = tx0 + ((v >> 4) & 0xfff);
-      const bool ok = live && v >= 0 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-      blds16(r, ok ? (unsigned)((gy * W + gx) * 256 + (v & 15) * 16) : 0x80000000u, dst + i * 1024);
-    }
+    const bool live = tile < pt.end;
+    const TileAt t = tile_at(live ? tile : pt.beg, tiles_x, tiles_y);
+    ring.issue(make_rsrc(x + t.bb * img_i, (unsigned long)img_i * 2), t.tyi * S::TH - 1, t.txi * S::TW - 1, H, W, live, slot);
   };
   // halo pixel of (row r, tap a, column parity pxc, tap c) for lane lr: (r + 1 + py - a) * HC + lr + 1 + pxc - c
   const int lbase = (lr + HC * py) * ROWB + lg * 16;
   const int cb = ch0 + (odd ? 16 : 0) + 8 * (lg >> 1);
-  float* aux = (float*)(smem + 3 * BUF);
+  float* aux = (float*)(smem + 3 * S::BUF);
   if (tid < 64) aux[tid] = bias ? bias[tid] : 0.f;
   __syncthreads();
 
-  int tile = t_beg + wi, k = 0;
-  issue(tile, 0);
-  issue(tile + wpx, 1);
-  for (; tile < t_end; tile += wpx, k++) {
-    const int txi = tile % tiles_x, t2 = tile / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const auto ro = make_rsrc(out + bb * img_o, (unsigned long)img_o * 2);
-    if (k == 0) wait_vmcnt<PPW>();
-    else if (k == 1) wait_vmcnt<PPW + NS>();
-    else wait_vmcnt<NS + PPW + NS>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue(tile + 2 * wpx, (k + 2) % 3);
-    const char* hb = smem + (k % 3) * BUF + lbase;
+  int k = 0;
+  issue(pt.first, 0);
+  issue(pt.first + pt.stride, 1);
+  for (int tile = pt.first; tile < pt.end; tile += pt.stride, k++) {
+    const TileAt t = tile_at(tile, tiles_x, tiles_y);
+    const auto ro = make_rsrc(out + t.bb * img_o, (unsigned long)img_o * 2);
+    ring_wait<S::PPW, 16, 0>(k);                                    // 16 stores per tile per wave (2 classes x 8 rows)
+    issue(tile + 2 * pt.stride, (k + 2) % 3);
+    const char* hb = smem + (k % 3) * S::BUF + lbase;
 #pragma unroll
     for (int pxc = 0; pxc < 2; pxc++) {
       f32x4 acc[8][2];
@@ -519,37 +390,13 @@ __global__ void __launch_bounds__(256, 1) convT4s2_rw_kernel(const bf16* __restr
           for (int nb = 0; nb < 2; nb++)
             acc[r][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[pxc][s][nb], fa[r], acc[r][nb], 0, 0, 0);
       };
-      bf16x8 fa0[8], fa1[8];
-      rd(0, fa0);
-#pragma unroll
-      for (int s = 0; s < 16; s += 2) {
-        rd(s + 1, fa1);
-        __builtin_amdgcn_sched_barrier(0);
-        mm(s, fa0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + 2 < 16) rd(s + 2, fa0);
-        __builtin_amdgcn_sched_barrier(0);
-        mm(s + 1, fa1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const int gx = txi * TW + lr;
+      rw_steps<16, 8>(rd, mm);
+      const int gx = t.txi * S::TW + lr;
 #pragma unroll
       for (int r = 0; r < 8; r++) {
-        const int gy = tyi * TH + r;
+        const int gy = t.tyi * S::TH + r;
         const unsigned po = (gy < H && gx < W) ? (unsigned)(((2 * gy + py) * 2 * W + 2 * gx + pxc) * 128 + cb * 2) : 0x80000000u;
-        float o[8];
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          float v0 = acc[r][0][e], v1 = acc[r][1][e];
-          if (RELU) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
-          const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
-          o[e] = __uint_as_float(sw[0]);
-          o[4 + e] = __uint_as_float(sw[1]);
-        }
-        bf16x8 ob;
-#pragma unroll
-        for (int e = 0; e < 8; e++) ob[e] = (bf16)o[e];
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, ob), ro, po, 0, 0);
+        trade_store8<RELU>(acc[r][0], acc[r][1], ro, po);
       }
     }
   }
@@ -566,22 +413,23 @@ __global__ void __launch_bounds__(256, 1) convT4s2_rw_kernel(const bf16* __restr
 //     fragments, read straight from the conv-view pack; all waves share the tile's 4 x 16 pixels;
 //   * epilogue: lane-pair channel trade, one 16-B store per lane per 16-pixel row, column sums in fp32 (LDS atomics,
 //     one global add per channel and workgroup).
-namespace cs2 {
-constexpr int TH = 4, TW = 16, HR = 2 * TH + 2, HC = 2 * TW + 2, PX = HR * HC, ROWB = 144;
-constexpr int PIECES = ((PX * ROWB + 4095) / 4096) * 4, PPW = PIECES / 4, BUF = PIECES * 1024, LDS = 3 * BUF + 1024;
-static_assert(LDS <= 160 * 1024, "conv s2 LDS budget");
-}  // namespace cs2
+struct Cs2Shape {
+  static constexpr int TH = 4, TW = 16, HR = 2 * TH + 2, HC = 2 * TW + 2, PX = HR * HC;
+  static constexpr int ROWB = 144, CHUNKS = 8, GPIX = 128;                            // 9 slots of 16 B per pixel
+  static constexpr int PIECES = ((PX * ROWB + 4095) / 4096) * 4, PPW = PIECES / 4, BUF = PIECES * 1024, LDS = 3 * BUF + 1024;
+  static_assert(LDS <= 160 * 1024, "conv s2 LDS budget");
+  DEV static int slot(int c, int) { return c; }
+};
 __global__ void __launch_bounds__(256, 1) conv4s2_rw_kernel(const bf16* __restrict__ x, const bf16* __restrict__ w,
                                                              float* __restrict__ colsum, bf16* __restrict__ out, int H,
                                                              int W, int tiles_x, int tiles_y, int ntiles) {
-  using namespace cs2;
-  constexpr int NS = TH;                                            // stores per tile per wave
+  typedef Cs2Shape S;
+  constexpr int TH = S::TH, HC = S::HC, ROWB = S::ROWB;
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
   const int lr = lane & 15, lg = lane >> 4, odd = lg & 1;
   const int ch0 = 32 * wave;
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, wpx = (nwg + 7 - xcd) >> 3, wi = blockIdx.x >> 3;
-  const int t_beg = (int)((long)ntiles * xcd / 8), t_end = (int)((long)ntiles * (xcd + 1) / 8);
+  const PersistentTiles pt(ntiles);
   const int Hi = 2 * H, Wi = 2 * W;
   const long img_i = (long)Hi * Wi * 64, img_o = (long)H * W * 128;
   // wr[tap][kk][nb]: lane (lr, lg) holds w[co = ch0 + 16 nb + lr][tap][ci = 32 kk + 8 lg .. +7]
@@ -593,47 +441,29 @@ __global__ void __launch_bounds__(256, 1) conv4s2_rw_kernel(const bf16* __restri
 #pragma unroll
       for (int nb = 0; nb < 2; nb++)
         wr[tap][kk][nb] = *(const bf16x8*)(w + ((ch0 + nb * 16 + lr) * 16 + tap) * 64 + kk * 32 + lg * 8);
-  int dm[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const int b = (wave * PPW + i) * 1024 + lane * 16, px = b / ROWB, ch = (b % ROWB) >> 4;
-    dm[i] = (px < PX && ch < 8) ? ((px / HC) << 16) | ((px % HC) << 4) | ch : -1;
-  }
+  const HaloRing<S> ring(smem, wave, lane);
   auto issue = [&](int tile, int slot) {
-    const bool live = tile < t_end;
-    const int tc = live ? tile : t_beg;
-    const int txi = tc % tiles_x, t2 = tc / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const int iy0 = 2 * tyi * TH - 1, ix0 = 2 * txi * TW - 1;
-    const auto r = make_rsrc(x + bb * img_i, (unsigned long)img_i * 2);
-    char* dst = smem + slot * BUF + wave * PPW * 1024;
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      const int v = dm[i], gy = iy0 + (v >> 16), gx = ix0 + ((v >> 4) & 0xfff);
-      const bool ok = live && v >= 0 && (unsigned)gy < (unsigned)Hi && (unsigned)gx < (unsigned)Wi;
-      blds16(r, ok ? (unsigned)((gy * Wi + gx) * 128 + (v & 15) * 16) : 0x80000000u, dst + i * 1024);
-    }
+    const bool live = tile < pt.end;
+    const TileAt t = tile_at(live ? tile : pt.beg, tiles_x, tiles_y);
+    ring.issue(make_rsrc(x + t.bb * img_i, (unsigned long)img_i * 2), 2 * t.tyi * TH - 1, 2 * t.txi * S::TW - 1, Hi, Wi, live, slot);
   };
   // halo pixel of output (row r, column lr) and tap (ky, kx): (2 r + ky) * HC + 2 lr + kx
   const int lbase = 2 * lr * ROWB + lg * 16;
   const int cb = ch0 + (odd ? 16 : 0) + 8 * (lg >> 1);
-  float* aux = (float*)(smem + 3 * BUF);
+  float* aux = (float*)(smem + 3 * S::BUF);
   if (tid < 128) aux[tid] = 0.f;
   __syncthreads();
   float cs[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-  int tile = t_beg + wi, k = 0;
-  issue(tile, 0);
-  issue(tile + wpx, 1);
-  for (; tile < t_end; tile += wpx, k++) {
-    const int txi = tile % tiles_x, t2 = tile / tiles_x, tyi = t2 % tiles_y, bb = t2 / tiles_y;
-    const auto ro = make_rsrc(out + bb * img_o, (unsigned long)img_o * 2);
-    if (k == 0) wait_vmcnt<PPW>();
-    else if (k == 1) wait_vmcnt<PPW + NS>();
-    else wait_vmcnt<NS + PPW + NS>();
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    issue(tile + 2 * wpx, (k + 2) % 3);
-    const char* hb = smem + (k % 3) * BUF + lbase;
+  int k = 0;
+  issue(pt.first, 0);
+  issue(pt.first + pt.stride, 1);
+  for (int tile = pt.first; tile < pt.end; tile += pt.stride, k++) {
+    const TileAt t = tile_at(tile, tiles_x, tiles_y);
+    const auto ro = make_rsrc(out + t.bb * img_o, (unsigned long)img_o * 2);
+    ring_wait<S::PPW, TH, 0>(k);                                    // TH stores per tile per wave
+    issue(tile + 2 * pt.stride, (k + 2) % 3);
+    const char* hb = smem + (k % 3) * S::BUF + lbase;
     f32x4 acc[TH][2];
 #pragma unroll
     for (int r = 0; r < TH; r++) { acc[r][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[r][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -649,84 +479,47 @@ __global__ void __launch_bounds__(256, 1) conv4s2_rw_kernel(const bf16* __restri
         for (int nb = 0; nb < 2; nb++)
           acc[r][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wr[s >> 1][s & 1][nb], fa[r], acc[r][nb], 0, 0, 0);
     };
-    bf16x8 fa0[TH], fa1[TH];
-    rd(0, fa0);
-#pragma unroll
-    for (int s = 0; s < 32; s += 2) {
-      rd(s + 1, fa1);
-      __builtin_amdgcn_sched_barrier(0);
-      mm(s, fa0);
-      __builtin_amdgcn_sched_barrier(0);
-      if (s + 2 < 32) rd(s + 2, fa0);
-      __builtin_amdgcn_sched_barrier(0);
-      mm(s + 1, fa1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    const int gx = txi * TW + lr;
+    rw_steps<32, TH>(rd, mm);
+    const int gx = t.txi * S::TW + lr;
 #pragma unroll
     for (int r = 0; r < TH; r++) {
-      const int gy = tyi * TH + r;
+      const int gy = t.tyi * TH + r;
       const bool ok = gy < H && gx < W;
       const unsigned po = ok ? (unsigned)(((gy * W + gx) * 128 + cb) * 2) : 0x80000000u;
-      float o[8];
+      trade_store8<false>(acc[r][0], acc[r][1], ro, po, [&](float (&o)[8]) {
+        if (ok) {
 #pragma unroll
-      for (int e = 0; e < 4; e++) {
-        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(acc[r][0][e]), __float_as_uint(acc[r][1][e]), false, false);
-        o[e] = __uint_as_float(sw[0]);
-        o[4 + e] = __uint_as_float(sw[1]);
-      }
-      if (ok) {
-#pragma unroll
-        for (int e = 0; e < 8; e++) cs[e] += o[e];
-      }
-      bf16x8 ob;
-#pragma unroll
-      for (int e = 0; e < 8; e++) ob[e] = (bf16)o[e];
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4v, ob), ro, po, 0, 0);
+          for (int e = 0; e < 8; e++) cs[e] += o[e];
+        }
+      });
     }
   }
-  if (colsum) {
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-      float c = cs[e];
-      c += __shfl_xor(c, 1); c += __shfl_xor(c, 2); c += __shfl_xor(c, 4); c += __shfl_xor(c, 8);
-      if (lr == 0) atomicAdd(aux + cb + e, c);
-    }
-    __syncthreads();
-    if (tid < 128) atomicAdd(colsum + tid, aux[tid]);
-  }
+  if (colsum) flush_colsum<128>(cs, aux, colsum, cb);
   wait_vmcnt<0>();
 }
 int conv4s2_rw_launch(const bf16* x, const bf16* w, float* colsum, bf16* out, int B, int H, int W, hipStream_t st) {
-  auto kfn = conv4s2_rw_kernel;
-  static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, cs2::LDS), true);   // once per process (thread-safe static init)
-  (void)attr;
-  const int tx = cdiv(W, cs2::TW), ty = cdiv(H, cs2::TH);
+  typedef Cs2Shape S;
+  const int tx = cdiv(W, S::TW), ty = cdiv(H, S::TH);
   const long tiles = (long)B * tx * ty;
-  if (tiles >= (1L << 31)) { s3od_set_error("conv s2 rw: too many tiles"); return 22; }
-  const int nwg = (int)std::min<long>(std::max<long>(tiles, 8), (long)s3od_cu_count());
-  hipLaunchKernelGGL(kfn, dim3(nwg), dim3(256), cs2::LDS, st, x, w, colsum, out, H, W, tx, ty, (int)tiles);
-  return s3od_check_launch("conv4s2_rw");
+  return launch_tiled<conv4s2_rw_kernel, S::LDS, 256>("conv4s2_rw", "conv s2 rw: too many tiles", tiles, grid_xcd(tiles), st,
+                                                      x, w, colsum, out, H, W, tx, ty, (int)tiles);
 }
 
 // S3OD_CONVT_RW=0 disables the path (under S3OD_AB=1: per call)
 bool convt_rw_ok(int dtype, int B, int H, int W) {
   return dtype == S3OD_BF16 && !S3OD_OFF("S3OD_CONVT_RW") && B > 0 && (long)4 * H * W * 128 < (1L << 31);
 }
-int convT4s2_rw_launch(const bf16* x, const bf16* wt, const float* bias, bool relu, bf16* out, int B, int H, int W,
-                           hipStream_t st) {
-  auto kfn = relu ? convT4s2_rw_kernel<true> : convT4s2_rw_kernel<false>;
-  static const bool attr0 = ((void)hipFuncSetAttribute((const void*)convT4s2_rw_kernel<false>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, ct::LDS), true);
-  static const bool attr1 = ((void)hipFuncSetAttribute((const void*)convT4s2_rw_kernel<true>,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, ct::LDS), true);
-  (void)attr0; (void)attr1;
-  const int tx = cdiv(W, ct::TW), ty = cdiv(H, ct::TH);
+template <bool RELU>
+static int launch_convT(const bf16* x, const bf16* wt, const float* bias, bf16* out, int B, int H, int W, hipStream_t st) {
+  typedef CtShape S;
+  const int tx = cdiv(W, S::TW), ty = cdiv(H, S::TH);
   const long tiles = (long)B * tx * ty;
-  if (tiles >= (1L << 31)) { s3od_set_error("convT rw: too many tiles"); return 22; }
-  const int nwg = (int)std::min<long>(std::max<long>(tiles, 8), (long)s3od_cu_count());   // >= 8: every XCD owns a tile range
-  hipLaunchKernelGGL(kfn, dim3(nwg), dim3(256), ct::LDS, st, x, wt, bias, out, H, W, tx, ty, (int)tiles);
-  return s3od_check_launch("convT4s2_rw");
+  return launch_tiled<convT4s2_rw_kernel<RELU>, S::LDS, 256>("convT4s2_rw", "convT rw: too many tiles", tiles, grid_xcd(tiles),
+                                                             st, x, wt, bias, out, H, W, tx, ty, (int)tiles);
+}
+int convT4s2_rw_launch(const bf16* x, const bf16* wt, const float* bias, bool relu, bf16* out, int B, int H, int W,
+                       hipStream_t st) {
+  return relu ? launch_convT<true>(x, wt, bias, out, B, H, W, st) : launch_convT<false>(x, wt, bias, out, B, H, W, st);
 }
 
 // ---------------------------------------------------------------- halo-tile 3x3 weight gradient
@@ -754,15 +547,12 @@ template <int CO> DEV int dy_at(int row, int byte) {       // conflict-free for 
   else return row * 192 + ((((byte >> 4) ^ ((row >> 1) & 3)) << 4) | (byte & 15));
 }
 DEV int hx_at(int row, int byte) { return row * 128 + ((((byte >> 4) ^ (row & 7)) << 4) | (byte & 15)); }
-// 16 columns x 32 rows fragment, transposed (rows = K, permuted: 4g + q and 16 + 4g + q)
-template <class AT> DEV bf16x8 trf(const char* img, int r0, int col0, int lane, AT at) {
+// 16 columns x 32 rows fragment, transposed (rows = K, permuted: 4g + q and 16 + 4g + q), of an image with PITCH bytes
+// per row: the swizzles of dy_at / hx_at repeat every 8 rows, so row + 16 lies 16 PITCH bytes on in the same slot
+template <int PITCH, class AT> DEV bf16x8 trf(const char* img, int r0, int col0, int lane, AT at) {
   const int g = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3;
   const int byte = (col0 + 4 * p) * 2;
-  typedef __attribute__((address_space(3))) s16x4 lds4;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(img + at(r0 + 4 * g + q, byte)));
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(img + at(r0 + 16 + 4 * g + q, byte)));
-  bf16x4 a = __builtin_bit_cast(bf16x4, lo), b = __builtin_bit_cast(bf16x4, hi);
-  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return trf_at<16 * PITCH>((const lds_char*)(img + at(r0 + 4 * g + q, byte)));
 }
 
 template <int CO, bool RELU>
@@ -775,11 +565,8 @@ conv3x3_wgrad_halo_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
   char* dyi = smem;
   char* hxi = smem + S::DYB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // channel block of this workgroup: (co0 .. co0+CO) x (ci0 .. ci0+64) of a CoT x CinT conv; the wpc
-  // workgroups of one block split the tiles into contiguous ranges (neighbouring tiles share halo rows)
-  const int combo = blockIdx.x / wpc, wi = blockIdx.x - combo * wpc;
-  const int co0 = (combo / nci) * CO, ci0 = (combo % nci) * 64;
-  const int t_beg = (int)((long)ntiles * wi / wpc), t_end = (int)((long)ntiles * (wi + 1) / wpc);
+  const ChannelBlock cbk(CO, ntiles, nci, wpc);
+  const int co0 = cbk.co0, ci0 = cbk.ci0, t_end = cbk.t_end;
   constexpr int NP = 9;                                  // (tap, ci-block) pairs of this wave: 9*wave ..
   const int pair0 = NP * wave;
   f32x4 acc[NP][NCO];
@@ -789,8 +576,8 @@ conv3x3_wgrad_halo_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
     for (int j = 0; j < NCO; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   uint4 pf[S::PT];
   auto prefetch = [&](int tile) {
-    const int txi = tile % tiles_x, t2 = tile / tiles_x, tyi = t2 % tiles_y, b = t2 / tiles_y;
-    const int ty0 = tyi * HT_TH, tx0 = txi * HT_TW;
+    const TileAt t = tile_at(tile, tiles_x, tiles_y);
+    const int ty0 = t.tyi * HT_TH, tx0 = t.txi * HT_TW, b = t.bb;
 #pragma unroll
     for (int i = 0; i < S::PT; i++) {
       const int c = tid + S::NT * i;
@@ -808,7 +595,7 @@ conv3x3_wgrad_halo_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
       }
     }
   };
-  int tile = t_beg;
+  int tile = cbk.t_beg;
   if (tile < t_end) prefetch(tile);
   for (; tile < t_end; tile++) {
 #pragma unroll
@@ -822,43 +609,29 @@ conv3x3_wgrad_halo_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
     for (int ty = 0; ty < HT_TH; ty++) {                  // K step = one output row of 32 pixels
       bf16x8 fa[NCO];
 #pragma unroll
-      for (int cb = 0; cb < NCO; cb++) fa[cb] = trf(dyi, ty * HT_TW, cb * 16, lane, dy_at<CO>);
+      for (int cb = 0; cb < NCO; cb++) fa[cb] = trf<CO * 2>(dyi, ty * HT_TW, cb * 16, lane, dy_at<CO>);
 #pragma unroll
       for (int j = 0; j < NP; j++) {
         const int pr = pair0 + j, tap = pr >> 2, cib = pr & 3, tdy = tap / 3, tdx = tap - tdy * 3;
-        const bf16x8 fb = trf(hxi, (ty + tdy) * HT_HC + tdx, cib * 16, lane, hx_at);
+        const bf16x8 fb = trf<128>(hxi, (ty + tdy) * HT_HC + tdx, cib * 16, lane, hx_at);
 #pragma unroll
         for (int cb = 0; cb < NCO; cb++) acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[cb], fb, acc[j][cb], 0, 0, 0);
       }
     }
     __syncthreads();
   }
-  // flush: lane holds D[co = cb*16 + 4g + r][ci = cib*16 + li] of pair j -> ws[co][tap*64 + ci]
-  const int g = lane >> 4, li = lane & 15;
-#pragma unroll
-  for (int j = 0; j < NP; j++) {
-    const int pr = pair0 + j, tap = pr >> 2, cib = pr & 3;
-#pragma unroll
-    for (int cb = 0; cb < NCO; cb++)
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        atomicAdd(ws + (long)(co0 + cb * 16 + 4 * g + r) * (9 * CinT) + tap * CinT + ci0 + cib * 16 + li, acc[j][cb][r]);
-  }
+  flush_wgrad<9, false>(acc, ws, co0, ci0, CinT, CoT, lane, pair0, 1);
 }
 
 template <int CO, bool RELU>
 static int launch_wgrad_halo(const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT, hipStream_t st) {
   typedef WgShape<CO> S;
-  auto kfn = conv3x3_wgrad_halo_kernel<CO, RELU>;
-  static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, S::LDS), true);   // once per process (thread-safe static init)
-  (void)attr;
   const int tx = cdiv(W, HT_TW), ty = cdiv(H, HT_TH);
   const long tiles = (long)B * tx * ty;
-  // one persistent workgroup per CU (registers) over all channel blocks: each block gets ~ncu/blocks of them
-  const int nci = CinT / 64, nblk = (CoT / CO) * nci;
-  const int wpc = (int)std::max<long>(1, std::min<long>(tiles, std::max(1, s3od_cu_count() / nblk)));
-  hipLaunchKernelGGL(kfn, dim3(nblk * wpc), dim3(S::NT), S::LDS, st, dy, x, ws, H, W, tx, ty, (int)tiles, CinT, CoT, nci, wpc);
-  return s3od_check_launch("conv3x3_wgrad_halo");
+  const int nci = CinT / 64, nblk = (CoT / CO) * nci, wpc = grid_wpc(tiles, nblk);
+  return launch_tiled<conv3x3_wgrad_halo_kernel<CO, RELU>, S::LDS, S::NT>(
+      "conv3x3_wgrad_halo", "wgrad halo: too many tiles", tiles, nblk * wpc, st, dy, x, ws, H, W, tx, ty, (int)tiles, CinT, CoT,
+      nci, wpc);
 }
 // CoT a multiple of 64 (64-channel output blocks) or 96 (the mask heads: one 96-channel block)
 int wgrad3x3_halo_launch(bool relu_x, const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT,
@@ -883,14 +656,13 @@ static_assert(AB % 1024 == 0 && LDS <= 160 * 1024, "wgrad 4s2 layout");
 }  // namespace wg4
 __global__ void __launch_bounds__(256, 1)
 conv4s2_wgrad_dma_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x, float* __restrict__ ws, int OH, int OW,
-                         int tiles_x, int tiles_y, int ntiles, int CinT, int CoT, int nci, int wpc, int ymaj) {
+                         int tiles_x, int tiles_y, int ntiles, int CinT, int CoT, int nci, int wpc) {
   using namespace wg4;
   constexpr int NCO = 4, NP = 16;
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-  const int combo = blockIdx.x / wpc, wi = blockIdx.x - combo * wpc;
-  const int t_beg = (int)((long)ntiles * wi / wpc), t_end = (int)((long)ntiles * (wi + 1) / wpc);
-  const int co0 = (combo / nci) * 64, ci0 = (combo % nci) * 64;
+  const ChannelBlock cbk(64, ntiles, nci, wpc);
+  const int co0 = cbk.co0, ci0 = cbk.ci0, t_end = cbk.t_end;
   const int pair0 = NP * wave, IH = 2 * OH, IW = 2 * OW;
   f32x4 acc[NP][NCO];
 #pragma unroll
@@ -912,11 +684,8 @@ conv4s2_wgrad_dma_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x
     }
   }
   auto issue = [&](int tile, int slot) {
-    // ymaj: consecutive tiles walk down a column (the halo's top 2 of 6 rows were the previous tile's: L2)
-    int txi, tyi, b;
-    if (ymaj) { tyi = tile % tiles_y; const int t2 = tile / tiles_y; txi = t2 % tiles_x; b = t2 / tiles_x; }
-    else { txi = tile % tiles_x; const int t2 = tile / tiles_x; tyi = t2 % tiles_y; b = t2 / tiles_y; }
-    const int oy0 = tyi * TH, ox0 = txi * TW;
+    const TileAt t = tile_at_ymaj(tile, tiles_x, tiles_y);
+    const int oy0 = t.tyi * TH, ox0 = t.txi * TW, b = t.bb;
     const long img_d = (long)OH * OW * CoT, img_x = (long)IH * IW * CinT;
     const auto rd = make_rsrc(dy + b * img_d, (unsigned long)img_d * 2);
     const auto rx = make_rsrc(x + b * img_x, (unsigned long)img_x * 2);
@@ -935,7 +704,7 @@ conv4s2_wgrad_dma_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x
       }
     }
   };
-  int tile = t_beg, k = 0;
+  int tile = cbk.t_beg, k = 0;
   if (tile < t_end) issue(tile, 0);
   for (; tile < t_end; tile++, k++) {
     wait_vmcnt<0>();
@@ -947,38 +716,23 @@ conv4s2_wgrad_dma_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x
     for (int ty = 0; ty < TH; ty++) {                     // K step = one dy row of 32 pixels
       bf16x8 fa[NCO];
 #pragma unroll
-      for (int cb = 0; cb < NCO; cb++) fa[cb] = trf(dyi, ty * TW, cb * 16, lane, dy_at<64>);
+      for (int cb = 0; cb < NCO; cb++) fa[cb] = trf<128>(dyi, ty * TW, cb * 16, lane, dy_at<64>);
 #pragma unroll
       for (int j = 0; j < NP; j++) {
         const int pr = pair0 + j, tap = pr >> 2, cib = pr & 3, ky = tap >> 2, kx = tap & 3;
         // halo column 2 k + kx of halo row 2 ty + ky = sub-row (kx & 1), entry k + (kx >> 1)
-        const bf16x8 fb = trf(hxi, ((2 * ty + ky) * 2 + (kx & 1)) * HS + (kx >> 1), cib * 16, lane, hx_at);
+        const bf16x8 fb = trf<128>(hxi, ((2 * ty + ky) * 2 + (kx & 1)) * HS + (kx >> 1), cib * 16, lane, hx_at);
 #pragma unroll
         for (int cb = 0; cb < NCO; cb++) acc[j][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[cb], fb, acc[j][cb], 0, 0, 0);
       }
     }
   }
-  const int g = lane >> 4, li = lane & 15;
-#pragma unroll
-  for (int j = 0; j < NP; j++) {
-    const int pr = pair0 + j, tap = pr >> 2, cib = pr & 3;
-#pragma unroll
-    for (int cb = 0; cb < NCO; cb++)
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        atomicAdd(ws + (long)(co0 + cb * 16 + 4 * g + r) * (16 * CinT) + tap * CinT + ci0 + cib * 16 + li, acc[j][cb][r]);
-  }
+  flush_wgrad<16, false>(acc, ws, co0, ci0, CinT, CoT, lane, pair0, 1);
 }
 int wgrad4s2_dma_launch(const bf16* dy, const bf16* x, float* ws, int B, int OH, int OW, int CinT, int CoT, hipStream_t st) {
-  auto kfn = conv4s2_wgrad_dma_kernel;
-  static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, wg4::LDS), true);   // once per process (thread-safe static init)
-  (void)attr;
   const int tx = cdiv(OW, wg4::TW), ty = cdiv(OH, wg4::TH);
   const long tiles = (long)B * tx * ty;
-  if (tiles >= (1L << 31)) { s3od_set_error("wgrad 4s2: too many tiles"); return 22; }
-  const int nci = CinT / 64, nblk = (CoT / 64) * nci;
-  const int wpc = (int)std::max<long>(1, std::min<long>(tiles, std::max(1, s3od_cu_count() / nblk)));
-  hipLaunchKernelGGL(kfn, dim3(nblk * wpc), dim3(256), wg4::LDS, st, dy, x, ws, OH, OW, tx, ty, (int)tiles, CinT, CoT, nci, wpc,
-                     1);   // ymaj, the only order launched
-  return s3od_check_launch("conv4s2_wgrad_dma");
+  const int nci = CinT / 64, nblk = (CoT / 64) * nci, wpc = grid_wpc(tiles, nblk);
+  return launch_tiled<conv4s2_wgrad_dma_kernel, wg4::LDS, 256>("conv4s2_wgrad_dma", "wgrad 4s2: too many tiles", tiles, nblk * wpc,
+                                                               st, dy, x, ws, OH, OW, tx, ty, (int)tiles, CinT, CoT, nci, wpc);
 }

@@ -3,8 +3,7 @@
 // Its own translation unit: built WITHOUT -amdgpu-mfma-vgpr-form=1 (Makefile), so the 144 accumulators live in
 // AGPRs and the 256 VGPRs hold the fragment bases, the DMA offsets and the operand fragments -- in the VGPR form
 // the same loop spilled 44 VGPRs and ran ~140 VALU (AGPR copies) per 576 MFMAs, ~50 without.
-#include "gemm.hpp"
-#include "conv_kernels.hpp"
+#include "conv_rw.hpp"
 #include <type_traits>
 #include <utility>
 
@@ -16,16 +15,6 @@ namespace wgd {
 constexpr int DYB = 256 * 128, HXB = HT_PX * 128, PIECES = 76, PPW = PIECES / 4, BUF = PIECES * 1024, LDS = 2 * BUF;
 static_assert(DYB % 1024 == 0 && DYB + HXB <= BUF && LDS <= 160 * 1024, "wgrad dma layout");
 }  // namespace wgd
-// Transposed 16 x 32 fragment (rows = K) at a precomputed per-lane LDS address (lo rows) + 2048 (hi rows, 16 rows on)
-typedef __attribute__((address_space(3))) char lds_char;
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-DEV bf16x8 trf_at(const lds_char* a) {
-  typedef __attribute__((address_space(3))) s16x4 lds4;
-  s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)a);
-  s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4*)(a + 2048));
-  bf16x4 x = __builtin_bit_cast(bf16x4, lo), y = __builtin_bit_cast(bf16x4, hi);
-  return bf16x8{x[0], x[1], x[2], x[3], y[0], y[1], y[2], y[3]};
-}
 // One 32-pixel row (K step TY) of a tile.  Wave w owns ci-block w and all 9 taps x 4 co-blocks, so the taps are
 // compile-time constants and every fragment address is a per-lane base + an immediate: the dy fragment of co-block
 // cb at fa[cb] + 4096 TY, the x-halo fragment of tap (dy, dx) at hb[r & 7] + 128 r with r = (TY + dy) 34 + dx
@@ -35,11 +24,11 @@ template <bool RELU, int TY>
 DEV void wgd_row(const lds_char* sb, const unsigned (&fa_b)[4], const unsigned (&hb)[8], f32x4 (&acc)[9][4]) {
   bf16x8 fa[4];
 #pragma unroll
-  for (int cb = 0; cb < 4; cb++) fa[cb] = trf_at(sb + fa_b[cb] + TY * HT_TW * 128);
+  for (int cb = 0; cb < 4; cb++) fa[cb] = trf_at<2048>(sb + fa_b[cb] + TY * HT_TW * 128);
 #pragma unroll
   for (int tap = 0; tap < 9; tap++) {
     const int r = (TY + tap / 3) * HT_HC + tap % 3;
-    bf16x8 fb = trf_at(sb + hb[r & 7] + r * 128);
+    bf16x8 fb = trf_at<2048>(sb + hb[r & 7] + r * 128);
     if constexpr (RELU) fb = __builtin_bit_cast(bf16x8, relu16<bf16>(__builtin_bit_cast(uint4, fb)));
 #pragma unroll
     for (int cb = 0; cb < 4; cb++) acc[tap][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[cb], fb, acc[tap][cb], 0, 0, 0);
@@ -68,16 +57,15 @@ static_assert(HT_TH == 8, "wgd rows");
 template <bool RELU, int NPROD>
 __global__ void __launch_bounds__(64 * (4 + NPROD), 1)
 conv3x3_wgrad_dmap_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x, float* __restrict__ ws, int H, int W,
-                          int tiles_x, int tiles_y, int ntiles, int CinT, int CoT, int nci, int wpc, int ymaj) {
+                          int tiles_x, int tiles_y, int ntiles, int CinT, int CoT, int nci, int wpc) {
   using namespace wgd;
   constexpr int NCO = 4, NP = 9, DP = DYB / 1024, HP = PIECES - DP;    // 32 dy + 44 halo pieces
   constexpr int DPP = DP / NPROD, HPP = HP / NPROD;                    // per producer
   static_assert(HP * 8 >= HT_PX && DP % NPROD == 0 && HP % NPROD == 0, "wgrad dma pieces");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_id();
-  const int combo = blockIdx.x / wpc, wi = blockIdx.x - combo * wpc;
-  const int t_beg = (int)((long)ntiles * wi / wpc), t_end = (int)((long)ntiles * (wi + 1) / wpc);
-  const int co0 = (combo / nci) * 64, ci0 = (combo % nci) * 64;
+  const ChannelBlock cbk(64, ntiles, nci, wpc);
+  const int co0 = cbk.co0, ci0 = cbk.ci0, t_beg = cbk.t_beg, t_end = cbk.t_end;
   if (wave >= 4) {
     // producer pw takes dy pieces pw + NPROD i and halo pieces pw + NPROD j
     const int pw = wave - 4;
@@ -94,12 +82,8 @@ conv3x3_wgrad_dmap_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
       hcode[j / 8] |= code << (4 * (j % 8));
     }
     auto issue = [&](int tile, int slot) __attribute__((always_inline)) {
-      // ymaj: a workgroup's consecutive tiles walk DOWN a column of tiles, so each halo shares its top 2 rows with the
-      // previous tile's (read moments ago: L2) -- 8 of 10 halo rows per tile from HBM instead of 10
-      int txi, tyi, b;
-      if (ymaj) { tyi = tile % tiles_y; const int t2 = tile / tiles_y; txi = t2 % tiles_x; b = t2 / tiles_x; }
-      else { txi = tile % tiles_x; const int t2 = tile / tiles_x; tyi = t2 % tiles_y; b = t2 / tiles_y; }
-      const int ty0 = tyi * HT_TH, tx0 = txi * HT_TW;
+      const TileAt t = tile_at_ymaj(tile, tiles_x, tiles_y);
+      const int ty0 = t.tyi * HT_TH, tx0 = t.txi * HT_TW, b = t.bb;
       const long img_d = (long)H * W * CoT, img_x = (long)H * W * CinT;
       const long od = ((long)ty0 * W + tx0) * CoT + co0, ox = ((long)(ty0 - 1) * W + tx0 - 1) * CinT + ci0;
       const auto rd = make_rsrc(dy + b * img_d + od, (unsigned long)(img_d - od) * 2);
@@ -186,30 +170,18 @@ conv3x3_wgrad_dmap_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ 
     tile_step(std::integral_constant<int, 1>{});
   }
   if (tile < t_end) tile_step(std::integral_constant<int, 0>{});
-  const int g = lane >> 4, li = lane & 15;
-#pragma unroll
-  for (int t = 0; t < NP; t++)
-#pragma unroll
-    for (int cb = 0; cb < NCO; cb++)
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        if (co0 + cb * 16 + 4 * g + r < CoT)               // (CoT = 96: the second block's top half is padding)
-          atomicAdd(ws + (long)(co0 + cb * 16 + 4 * g + r) * (9 * CinT) + t * CinT + ci0 + wave * 16 + li, acc[t][cb][r]);
+  flush_wgrad<9, true>(acc, ws, co0, ci0, CinT, CoT, lane, wave, 4);
 }
 
 template <bool RELU>
 static int launch_wgrad_dma(const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT, hipStream_t st) {
   constexpr int NPROD = 2;
-  auto kfn = conv3x3_wgrad_dmap_kernel<RELU, NPROD>;
-  static const bool attr = ((void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, wgd::LDS), true);   // once per process (thread-safe static init)
-  (void)attr;
   const int tx = cdiv(W, HT_TW), ty = cdiv(H, HT_TH);
   const long tiles = (long)B * tx * ty;
-  const int nci = CinT / 64, nblk = cdiv(CoT, 64) * nci;
-  const int wpc = (int)std::max<long>(1, std::min<long>(tiles, std::max(1, s3od_cu_count() / nblk)));
-  hipLaunchKernelGGL(kfn, dim3(nblk * wpc), dim3(64 * (4 + NPROD)), wgd::LDS, st, dy, x, ws, H, W, tx, ty, (int)tiles, CinT, CoT,
-                     nci, wpc, 1);   // ymaj, the only order launched
-  return s3od_check_launch("conv3x3_wgrad_dma");
+  const int nci = CinT / 64, nblk = cdiv(CoT, 64) * nci, wpc = grid_wpc(tiles, nblk);
+  return launch_tiled<conv3x3_wgrad_dmap_kernel<RELU, NPROD>, wgd::LDS, 64 * (4 + NPROD)>(
+      "conv3x3_wgrad_dma", "wgrad dma: too many tiles", tiles, nblk * wpc, st, dy, x, ws, H, W, tx, ty, (int)tiles, CinT, CoT, nci,
+      wpc);
 }
 
 int wgrad3x3_dma_launch(bool relu_x, const bf16* dy, const bf16* x, float* ws, int B, int H, int W, int CinT, int CoT,
