@@ -22,15 +22,8 @@
 //
 // Backward: bf16 on v_mfma_f32_32x32x16_bf16 (attn_bwd_dkdv32_kernel, attn_bwd_dq32_kernel); f32 on
 // v_mfma_f32_16x16x4_f32 (attn_bwd_dkdv_kernel, attn_bwd_dq_kernel: the strict-parity path only, no bf16 instance).
-#include "common.hpp"
+#include "reduce.hpp"
 #include <type_traits>
-
-#define DISPATCH_T(dtype, ...)                                                  \
-  do {                                                                          \
-    if ((dtype) == S3OD_BF16) { typedef bf16 T; __VA_ARGS__ }                   \
-    else if ((dtype) == S3OD_F32) { typedef float T; __VA_ARGS__ }              \
-    else { s3od_set_error("bad dtype %d", (int)(dtype)); return 22; }           \
-  } while (0)
 
 namespace {
 constexpr float LN2 = 0.6931471805599453f;
@@ -514,8 +507,8 @@ DEV void qkv_sink_row(const QkvSink& o, int which, int b, int h, int H, int tok,
     for (int i = 0; i < 4; i++) csum[ds][i] += out[ds][i];
   }
 }
-// sum the 16 row-lanes of each column group and add into replica `rep` of ws [q D | v D]
-DEV void qkv_sink_colsum(const QkvSink& o, int which, int h, int H, int rep, int lane, f32x4 (&csum)[4]) {
+// sum the 16 row-lanes of each column group and add into workgroup `block`'s replica of ws [q D | v D]
+DEV void qkv_sink_colsum(const QkvSink& o, int which, int h, int H, unsigned block, int lane, f32x4 (&csum)[4]) {
 #pragma unroll
   for (int ds = 0; ds < 4; ds++)
 #pragma unroll
@@ -526,7 +519,7 @@ DEV void qkv_sink_colsum(const QkvSink& o, int which, int h, int H, int rep, int
     }
   if ((lane & 15) == 0) {
     const int D = H * 64, g = lane >> 4;
-    float* dst = o.ws + (long)rep * 2 * D + (which == 0 ? 0 : D) + h * 64 + 4 * g;
+    float* dst = replica(o.ws, block, 2, D) + (which == 0 ? 0 : D) + h * 64 + 4 * g;
 #pragma unroll
     for (int ds = 0; ds < 4; ds++)
 #pragma unroll
@@ -659,7 +652,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkdv_kernel(const float* __restr
       qkv_sink_row(sink, 1, b, h, H, key, N, g, kv, LN2, csk);
       qkv_sink_row(sink, 2, b, h, H, key, N, g, vv, 1.f, csv);
     }
-    if (sink.ws) qkv_sink_colsum(sink, 2, h, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csv);
+    if (sink.ws) qkv_sink_colsum(sink, 2, h, H, blockIdx.y * gridDim.x + blockIdx.x, lane, csv);
     return;
   }
   // store: lane = key (li), rows d = ds*16 + 4g + i
@@ -787,7 +780,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const float* __restric
       const f32x4 qv[4] = {dq[0][qs], dq[1][qs], dq[2][qs], dq[3][qs]};
       qkv_sink_row(sink, 0, b, h, H, q, N, g, qv, 0.125f, csq);
     }
-    if (sink.ws) qkv_sink_colsum(sink, 0, h, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csq);
+    if (sink.ws) qkv_sink_colsum(sink, 0, h, H, blockIdx.y * gridDim.x + blockIdx.x, lane, csq);
     return;
   }
 #pragma unroll
@@ -916,12 +909,12 @@ DEV void qkv_sink32(const QkvSink& o, int which, int b, int hh, int H, int tok0,
     }
   }
 }
-DEV void qkv_colsum32(const QkvSink& o, int which, int hh, int H, int rep, int lane, float (&csum)[2]) {
+DEV void qkv_colsum32(const QkvSink& o, int which, int hh, int H, unsigned block, int lane, float (&csum)[2]) {
   const int D = H * 64;
 #pragma unroll
   for (int db = 0; db < 2; db++) {
     const float v = csum[db] + __shfl_xor(csum[db], 32);
-    if (lane < 32) atomicAdd(o.ws + (long)rep * 2 * D + (which == 0 ? 0 : D) + hh * 64 + 32 * db + lane, v);
+    if (lane < 32) atomicAdd(replica(o.ws, block, 2, D) + (which == 0 ? 0 : D) + hh * 64 + 32 * db + lane, v);
   }
 }
 }  // namespace
@@ -1078,7 +1071,7 @@ __global__ void __launch_bounds__(64 * W) attn_bwd_dkdv32_kernel(const bf16* __r
     float csk[2] = {0.f, 0.f}, csv[2] = {0.f, 0.f};
     qkv_sink32<bf16>(sink, 1, b, hh, H, k0, N, lane, dk, -LN2, csk);
     qkv_sink32<bf16>(sink, 2, b, hh, H, k0, N, lane, dv, 1.f, csv);
-    if (sink.ws) qkv_colsum32(sink, 2, hh, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csv);
+    if (sink.ws) qkv_colsum32(sink, 2, hh, H, blockIdx.y * gridDim.x + blockIdx.x, lane, csv);
     return;
   }
 #pragma unroll
@@ -1191,7 +1184,7 @@ __global__ void __launch_bounds__(64 * W) attn_bwd_dq32_kernel(const bf16* __res
   if (sink.dqkv) {
     float csq[2] = {0.f, 0.f};
     qkv_sink32<bf16>(sink, 0, b, hh, H, q0, N, lane, dq, -0.125f, csq);
-    if (sink.ws) qkv_colsum32(sink, 0, hh, H, (blockIdx.y * gridDim.x + blockIdx.x) % S3OD_NREP, lane, csq);
+    if (sink.ws) qkv_colsum32(sink, 0, hh, H, blockIdx.y * gridDim.x + blockIdx.x, lane, csq);
     return;
   }
 #pragma unroll
@@ -1234,15 +1227,6 @@ int s3od_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* 
 }  // extern "C"
 
 namespace {
-__global__ void qkv_fold_kernel(float* __restrict__ ws, float* __restrict__ a, float* __restrict__ b, int D) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 2 * D) return;
-  float s = 0.f;
-  for (int r = 0; r < S3OD_NREP; r++) { s += ws[(long)r * 2 * D + i]; ws[(long)r * 2 * D + i] = 0.f; }
-  if (i < D) { if (a) a[i] += s; }
-  else if (b) b[i - D] += s;
-}
-
 template <typename T>
 void launch_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse, float* delta,
                 void* dq, void* dk, void* dv, QkvSink sink, int B, int H, int N, hipStream_t st) {
@@ -1291,7 +1275,7 @@ int s3od_attn_bwd_qkv(int dtype, const void* q, const void* k, const void* v, co
   const int D = 64 * H;
   QkvSink sink{dqkv, cos_t, sin_t, ws, P};
   DISPATCH_T(dtype, { launch_bwd<T>(q, k, v, o, dout, lse, delta, nullptr, nullptr, nullptr, sink, B, H, N, st); });
-  if (ws) hipLaunchKernelGGL(qkv_fold_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, st, ws, dbq, dbv, D);
+  if (ws) replica_fold2(ws, dbq, dbv, D, st);
   return s3od_check_launch("attn_bwd_qkv");
 }
 }  // extern "C"

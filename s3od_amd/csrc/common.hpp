@@ -32,6 +32,14 @@ int s3od_check_launch(const char* what);
     }                                               \
   } while (0)
 
+// runs the statement block with T = bf16 / float for dtype S3OD_BF16 / S3OD_F32, inside an entry point that returns int
+#define DISPATCH_T(dtype, ...)                                                  \
+  do {                                                                          \
+    if ((dtype) == S3OD_BF16) { typedef bf16 T; __VA_ARGS__ }                   \
+    else if ((dtype) == S3OD_F32) { typedef float T; __VA_ARGS__ }              \
+    else { s3od_set_error("bad dtype %d", (int)(dtype)); return 22; }           \
+  } while (0)
+
 // ------------------------------------------------------------------ conversions
 template <typename T> DEV float to_f(T v);
 template <> DEV float to_f<float>(float v) { return v; }
@@ -50,6 +58,15 @@ template <> DEV void load8<bf16>(const bf16* p, float* v) {
   bf16x8 a = *(const bf16x8*)p;
 #pragma unroll
   for (int i = 0; i < 8; i++) v[i] = (float)a[i];
+}
+// 4 consecutive elements <-> floats (8 B for bf16, 16 B for f32)
+template <typename T> DEV void load4(const T* p, float* v) {
+  if constexpr (sizeof(T) == 4) { const float4 a = *(const float4*)p; v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; }
+  else {
+    const bf16x4 a = *(const bf16x4*)p;
+#pragma unroll
+    for (int i = 0; i < 4; i++) v[i] = (float)a[i];
+  }
 }
 template <typename T> DEV void store4(T* p, const float* v) {
   if constexpr (sizeof(T) == 4) *(float4*)p = make_float4(v[0], v[1], v[2], v[3]);
@@ -159,6 +176,9 @@ DEV void lds_barrier() { wait_lgkm0(); __builtin_amdgcn_s_barrier(); asm volatil
 // from ~1000 workgroups onto the same few KB serialise at the memory side (measured 2-3x slower
 // end to end for the BN backward / q,v-bias reductions).
 constexpr int S3OD_NREP = 32;
+// the replica of a [S3OD_NREP][n][D] accumulator (n vectors of D columns) that workgroup `block` adds into; reduce.hpp
+// folds the replicas
+template <typename A> DEV A* replica(A* ws, unsigned block, int n, int D) { return ws + (long)(int)(block % S3OD_NREP) * n * D; }
 
 // compute units of the current device (read once per process)
 static inline int s3od_cu_count() {

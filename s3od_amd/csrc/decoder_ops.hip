@@ -2,15 +2,8 @@
 // batch statistics / apply / backward, bilinear resize fwd/bwd, global average pool,
 // IoU-score MLP head fwd/bwd, mask-head backward prologue, ReLU masks.
 // Reference: src/s3od/model.py:109-467.
-#include "common.hpp"
+#include "reduce.hpp"
 #include <type_traits>
-
-#define DISPATCH_T(dtype, ...)                                                  \
-  do {                                                                          \
-    if ((dtype) == S3OD_BF16) { typedef bf16 T; __VA_ARGS__ }                   \
-    else if ((dtype) == S3OD_F32) { typedef float T; __VA_ARGS__ }              \
-    else { s3od_set_error("bad dtype %d", (int)(dtype)); return 22; }           \
-  } while (0)
 
 // ---------------------------------------------------------------- weight repack
 // src f32 [O][I][KH][KW] (PyTorch conv / conv-view of ConvTranspose) -> dst T [O][KH][KW][I]
@@ -31,6 +24,19 @@ __global__ void repack_kernel(const float* __restrict__ src, T* __restrict__ dst
 // data-gradient weight (dx = conv(dy, w^T flipped)), several tensors may interleave their columns;
 // mode 2: as mode 1 without the tap reversal (the ConvTranspose2d(4, s2) sub-pixel kernel's weight).
 constexpr int RPK_FIELDS = 8;
+// the general path over elements [o0, o1) of one tensor, with index arithmetic of type IDX
+template <typename IDX, typename T>
+DEV void repack_range(const float* __restrict__ src, T* __restrict__ dst, IDX o0, IDX o1, int O, int I, int KHW, int mode, long ld) {
+  for (IDX idx = o0 + threadIdx.x; idx < o1; idx += blockDim.x) {
+    if (mode == 0) {
+      const IDX i = idx % I, r = idx / I, tp = r % KHW, o = r / KHW;
+      dst[idx] = from_f<T>(src[(o * I + i) * KHW + tp]);
+    } else {
+      const IDX o = idx % O, r = idx / O, tp = r % KHW, i = r / KHW;
+      dst[((long)i * KHW + tp) * ld + o] = from_f<T>(src[(o * I + i) * KHW + (mode == 1 ? KHW - 1 - tp : tp)]);
+    }
+  }
+}
 template <typename T>
 __global__ void __launch_bounds__(256) repack_multi_kernel(const long* __restrict__ tab, const int* __restrict__ chunk_t,
                                                            const long* __restrict__ chunk_o, int chunk) {
@@ -57,27 +63,9 @@ __global__ void __launch_bounds__(256) repack_multi_kernel(const long* __restric
     for (long idx = o0 + 4 * n4 + threadIdx.x; idx < o1; idx += blockDim.x) dst[idx] = from_f<T>(src[idx]);
     return;
   }
-  if (total >= (1L << 31)) {                       // (no model tensor is this large) 64-bit index arithmetic
-    for (long idx = o0 + threadIdx.x; idx < o1; idx += blockDim.x) {
-      if (mode == 0) {
-        int i = idx % I; long r = idx / I; int tp = r % KHW; int o = r / KHW;
-        dst[idx] = from_f<T>(src[((long)o * I + i) * KHW + tp]);
-      } else {
-        int o = idx % O; long r = idx / O; int tp = r % KHW; int i = r / KHW;
-        dst[((long)i * KHW + tp) * ld + o] = from_f<T>(src[((long)o * I + i) * KHW + (mode == 1 ? KHW - 1 - tp : tp)]);
-      }
-    }
-    return;
-  }
-  for (int idx = (int)o0 + threadIdx.x; idx < (int)o1; idx += blockDim.x) {      // 32-bit index arithmetic
-    if (mode == 0) {
-      const int i = idx % I, r = idx / I, tp = r % KHW, o = r / KHW;
-      dst[idx] = from_f<T>(src[(o * I + i) * KHW + tp]);
-    } else {
-      const int o = idx % O, r = idx / O, tp = r % KHW, i = r / KHW;
-      dst[((long)i * KHW + tp) * ld + o] = from_f<T>(src[(o * I + i) * KHW + (mode == 1 ? KHW - 1 - tp : tp)]);
-    }
-  }
+  // 32-bit index arithmetic unless the tensor needs 64 (no model tensor is that large)
+  if (total >= (1L << 31)) repack_range<long>(src, dst, o0, o1, O, I, KHW, mode, ld);
+  else repack_range<int>(src, dst, (int)o0, (int)o1, O, I, KHW, mode, ld);
 }
 
 // ConvTranspose2d weight [Cin_T][Cout_T][KH][KW] IS the conv-view weight [cout_c][cin_c][KH][KW]; no flip.
@@ -101,14 +89,10 @@ __global__ void bn_finalize_kernel(double* stats, long count, const float* w, co
                                    float momentum, float eps, float* mean_o, float* rstd_o, float* scale, float* shift, int C) {
   int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-  for (int r = 0; r < S3OD_NREP; r++) {
-    double* st = stats + (long)r * 2 * C;
-    s1 += st[c]; s2 += st[C + c];
-    st[c] = 0.0; st[C + c] = 0.0;
-  }
-  double mean = s1 / (double)count;
-  double var = s2 / (double)count - mean * mean;
+  double s[2] = {0.0, 0.0};
+  replica_sum(stats, 2, C, {c, C + c}, s);
+  double mean = s[0] / (double)count;
+  double var = s[1] / (double)count - mean * mean;
   if (var < 0) var = 0;
   float rstd = (float)(1.0 / sqrt(var + (double)eps));
   mean_o[c] = (float)mean; rstd_o[c] = rstd;
@@ -142,22 +126,8 @@ __global__ void affine_act_kernel(const T* __restrict__ x, const float* __restri
 }
 
 // Row-blocked NHWC reductions: a 256-thread block = CG = C/8 column groups x (256/CG) row phases,
-// each thread owning 8 channels; per-thread partials are reduced over the row phases in LDS so a
-// block issues one atomic per channel (not one per thread).
-template <int NV> DEV void rowphase_reduce(float (&v)[NV][8], float* red, int t, int CG) {
-  const int nph = 256 / CG;
-#pragma unroll
-  for (int j = 0; j < NV; j++) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; e++) red[t * 8 + e] = v[j][e];
-    __syncthreads();
-    if (t < CG)
-      for (int q = 1; q < nph; q++)
-#pragma unroll
-        for (int e = 0; e < 8; e++) v[j][e] += red[(q * CG + t) * 8 + e];
-  }
-}
+// each thread owning 8 channels; per-thread partials are reduced over the row phases in LDS (phase_reduce,
+// reduce.hpp) so a block issues one atomic per channel (not one per thread).
 
 // ReLU masks of the BN backward.  MODE 0: none; 1: dy' = dy*(y>0) with y read back; 2: y recomputed
 // as T(fma(z, scale, shift)) — the exact value affine_act_kernel stored — so the y tensor is not read
@@ -176,6 +146,23 @@ template <typename T, int MODE> struct ReluMask {
   }
 };
 
+// What a thread of either BN-backward pass starts from: its column group (channels c .. c+7) and row phase ri of
+// `rows`, those channels' statistics, the ReLU mask and the block's pixel range [p0, p1)
+template <typename T, int MODE> struct BnBwdThread {
+  int cg, rows, ri, c;
+  float mu[8], rs[8];
+  ReluMask<T, MODE> rl;
+  long p0, p1;
+  DEV BnBwdThread(const T* y_relu, const float* as, const float* at, const float* mean, const float* rstd, long npix, int C,
+                  int pix_per_block) {
+    cg = C / 8; rows = 256 / cg;
+    ri = threadIdx.x / cg; c = threadIdx.x % cg * 8;
+    load8<float>(mean + c, mu); load8<float>(rstd + c, rs);
+    rl.init(y_relu, as, at, c);
+    p0 = (long)blockIdx.x * pix_per_block; p1 = min(npix, p0 + pix_per_block);
+  }
+};
+
 // BN backward, pass 1: per channel sums of dy' and dy'*xhat where dy' = dy masked by ReluMask,
 // xhat = (z - mean)*rstd.  Output double [2][C].  Main loop keeps 4 pixel rows of loads in flight.
 template <typename T, int MODE>
@@ -184,14 +171,11 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                      double* __restrict__ sums, long npix, int C, int pix_per_block) {
   __shared__ float red[256 * 8];
-  const int cg = C / 8, rows = 256 / cg;
-  const int t = threadIdx.x, cgi = t % cg, ri = t / cg;
-  const int c = cgi * 8;
-  float mu[8], rs[8];
-  load8<float>(mean + c, mu); load8<float>(rstd + c, rs);
-  ReluMask<T, MODE> rl; rl.init(y_relu, as, at, c);
+  const BnBwdThread<T, MODE> k(y_relu, as, at, mean, rstd, npix, C, pix_per_block);
+  const int t = threadIdx.x, cg = k.cg, rows = k.rows, c = k.c;
+  const auto& mu = k.mu; const auto& rs = k.rs; const auto& rl = k.rl;
+  const long p1 = k.p1;
   float acc[2][8] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
-  const long p0 = (long)blockIdx.x * pix_per_block, p1 = min(npix, p0 + pix_per_block);
   auto body = [&](const float* d0, const float* zz, const float* yy) {
 #pragma unroll
     for (int e = 0; e < 8; e++) {
@@ -200,7 +184,7 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
       acc[0][e] += d; acc[1][e] += d * xh;
     }
   };
-  long p = p0 + ri;
+  long p = k.p0 + k.ri;
   for (; p + 3 * rows < p1; p += 4 * rows) {
     float d[4][8], zz[4][8], yy[4][8];
 #pragma unroll
@@ -219,9 +203,9 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
     rl.load(o, yy);
     body(d, zz, yy);
   }
-  rowphase_reduce<2>(acc, red, t, cg);
+  phase_reduce<2>(acc, red, t, cg, rows);
   if (t < cg) {
-    double* rep = sums + (long)(blockIdx.x % S3OD_NREP) * 3 * C;
+    double* rep = replica(sums, blockIdx.x, 3, C);
 #pragma unroll
     for (int e = 0; e < 8; e++) { atomicAdd(rep + c + e, (double)acc[0][e]); atomicAdd(rep + C + c + e, (double)acc[1][e]); }
   }
@@ -231,9 +215,9 @@ __global__ void __launch_bounds__(256) bn_bwd_reduce_kernel(const T* __restrict_
 __global__ void bn_fold_replicas_kernel(double* sums, int C) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 2 * C) return;
-  double s = sums[i];
-  for (int r = 1; r < S3OD_NREP; r++) { s += sums[(long)r * 3 * C + i]; sums[(long)r * 3 * C + i] = 0.0; }
-  sums[i] = s;
+  double s[1] = {sums[i]};
+  replica_sum(sums, 3, C, {i}, s, 1);
+  sums[i] = s[0];
 }
 
 // BN backward, pass 2: dz = w*rstd*(dy' - s1/n - xhat*s2/n); optional dcb[c] += sum_p dz (the
@@ -245,18 +229,17 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__
                                     double* __restrict__ sums, T* __restrict__ dz, float* __restrict__ dcb,
                                     long npix, int C, int pix_per_block) {
   __shared__ float red[256 * 8];
-  const int cg = C / 8, rows = 256 / cg;
-  const int t = threadIdx.x, cgi = t % cg, ri = t / cg;
-  const int c = cgi * 8;
-  float mu[8], rs[8], k1[8], m1[8], m2[8];
+  const BnBwdThread<T, MODE> k(y_relu, as, at, mean, rstd, npix, C, pix_per_block);
+  const int t = threadIdx.x, cg = k.cg, rows = k.rows, c = k.c;
+  const auto& mu = k.mu; const auto& rs = k.rs; const auto& rl = k.rl;
+  const long p1 = k.p1;
+  float k1[8], m1[8], m2[8];
 #pragma unroll
   for (int e = 0; e < 8; e++) {
-    mu[e] = mean[c + e]; rs[e] = rstd[c + e]; k1[e] = w[c + e] * rs[e];
+    k1[e] = w[c + e] * rs[e];
     m1[e] = (float)(sums[c + e] / (double)npix); m2[e] = (float)(sums[C + c + e] / (double)npix);
   }
-  ReluMask<T, MODE> rl; rl.init(y_relu, as, at, c);
   float acc[1][8] = {{0, 0, 0, 0, 0, 0, 0, 0}};
-  const long p0 = (long)blockIdx.x * pix_per_block, p1 = min(npix, p0 + pix_per_block);
   auto body = [&](long o, const float* d0, const float* zz, const float* yy) {
     float out[8];
 #pragma unroll
@@ -270,7 +253,7 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__
   };
   // software-pipelined over 4-row batches: batch k+1's loads are issued before batch k's stores.  One vmcnt counts
   // loads and stores in issue order, so a batch loaded AFTER the previous batch's stores waited for those stores too.
-  long p = p0 + ri;
+  long p = k.p0 + k.ri;
   if (p + 3 * rows < p1) {
     Row8<T> cd[4], cz[4], cy[4];
     auto ld4 = [&](long pp, Row8<T> (&rd)[4], Row8<T> (&rz)[4], Row8<T> (&ry)[4]) {
@@ -308,9 +291,9 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const T* __restrict__
     body(o, d, zz, yy);
   }
   if (dcb) {
-    rowphase_reduce<1>(acc, red, t, cg);
+    phase_reduce<1>(acc, red, t, cg, rows);
     if (t < cg) {
-      double* rep = sums + (long)(blockIdx.x % S3OD_NREP) * 3 * C + 2 * C;
+      double* rep = replica(sums, blockIdx.x, 3, C) + 2 * C;
 #pragma unroll
       for (int e = 0; e < 8; e++) atomicAdd(rep + c + e, (double)acc[0][e]);
     }
@@ -325,9 +308,9 @@ __global__ void bn_param_grads_kernel(double* sums, float* dw, float* db, float*
   db[c] += (float)sums[c];
   dw[c] += (float)sums[C + c];
   sums[c] = 0.0; sums[C + c] = 0.0;
-  double s = 0.0;
-  for (int r = 0; r < S3OD_NREP; r++) { s += sums[(long)r * 3 * C + 2 * C + c]; sums[(long)r * 3 * C + 2 * C + c] = 0.0; }
-  if (dcb) dcb[c] += (float)s;
+  double s[1] = {0.0};
+  replica_sum(sums, 3, C, {2 * C + c}, s);
+  if (dcb) dcb[c] += (float)s[0];
 }
 
 // ---------------------------------------------------------------- bilinear (align_corners=False)
@@ -357,6 +340,14 @@ DEV void bil_coef_exact(int o, int in, int out, int& i0, int& i1, float& w0, flo
   w0 = 1.f - w1;
 }
 
+// the 4-tap blend of 8 channels: rows (a b) and (cc d) by the column weights, then by the row weights
+DEV void bil_blend(float wy0, float wy1, float wx0, float wx1, const float* a, const float* bb, const float* cc, const float* d, float* o) {
+#pragma unroll
+  for (int e = 0; e < 8; e++) o[e] = wy0 * (wx0 * a[e] + wx1 * bb[e]) + wy1 * (wx0 * cc[e] + wx1 * d[e]);
+}
+// weight of an output with taps (a0, a1), weights (u0, u1) on input i
+DEV float bil_weight_on(int i, int a0, int a1, float u0, float u1) { return (a0 == i ? u0 : 0.f) + (a1 == i ? u1 : 0.f); }
+
 template <typename T>
 __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int IH, int IW, int OH, int OW, int C) {
   long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
@@ -371,8 +362,7 @@ __global__ void bilinear_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, 
   float a[8], bb[8], cc[8], d[8], o[8];
   load8<T>(base + ((long)y0 * IW + x0) * C, a); load8<T>(base + ((long)y0 * IW + x1) * C, bb);
   load8<T>(base + ((long)y1 * IW + x0) * C, cc); load8<T>(base + ((long)y1 * IW + x1) * C, d);
-#pragma unroll
-  for (int e = 0; e < 8; e++) o[e] = wy0 * (wx0 * a[e] + wx1 * bb[e]) + wy1 * (wx0 * cc[e] + wx1 * d[e]);
+  bil_blend(wy0, wy1, wx0, wx1, a, bb, cc, d, o);
   store8<T>(y + i, o);
 }
 
@@ -404,11 +394,8 @@ __global__ void bilinear_up2_kernel(const T* __restrict__ x, T* __restrict__ y, 
     for (int dx = 0; dx < 2; dx++) {
       int x0, x1; float wx0, wx1;
       bil_coef(2 * j + dx, IW, OW, x0, x1, wx0, wx1);
-      const float* a = n[dy][dx]; const float* bb = n[dy][dx + 1];
-      const float* cc = n[dy + 1][dx]; const float* d = n[dy + 1][dx + 1];
       float o[8];
-#pragma unroll
-      for (int e = 0; e < 8; e++) o[e] = wy0 * (wx0 * a[e] + wx1 * bb[e]) + wy1 * (wx0 * cc[e] + wx1 * d[e]);
+      bil_blend(wy0, wy1, wx0, wx1, n[dy][dx], n[dy][dx + 1], n[dy + 1][dx], n[dy + 1][dx + 1], o);
       store8<T>(y + (((long)b * OH + 2 * k + dy) * OW + 2 * j + dx) * C + c, o);
     }
   }
@@ -443,11 +430,11 @@ __global__ void bilinear_bwd_kernel(const T* __restrict__ dy, const float* __res
       wy[t] = 0.f; wx[t] = 0.f;
       if (oy >= 0 && oy < OH) {
         int a0, a1; float u0, u1; bil_coef(oy, IH, OH, a0, a1, u0, u1);
-        wy[t] = (a0 == iy ? u0 : 0.f) + (a1 == iy ? u1 : 0.f);
+        wy[t] = bil_weight_on(iy, a0, a1, u0, u1);
       }
       if (ox >= 0 && ox < OW) {
         int c0, c1; float v0, v1; bil_coef(ox, IW, OW, c0, c1, v0, v1);
-        wx[t] = (c0 == ix ? v0 : 0.f) + (c1 == ix ? v1 : 0.f);
+        wx[t] = bil_weight_on(ix, c0, c1, v0, v1);
       }
       oyc[t] = min(max(oy, 0), OH - 1); oxc[t] = min(max(ox, 0), OW - 1);
     }
@@ -472,11 +459,11 @@ __global__ void bilinear_bwd_kernel(const T* __restrict__ dy, const float* __res
   }
   for (int oy = oy_lo; oy <= oy_hi; oy++) {
     int a0, a1; float u0, u1; bil_coef_exact(oy, IH, OH, a0, a1, u0, u1);
-    float wy = (a0 == iy ? u0 : 0.f) + (a1 == iy ? u1 : 0.f);
+    float wy = bil_weight_on(iy, a0, a1, u0, u1);
     if (wy == 0.f) continue;
     for (int ox = ox_lo; ox <= ox_hi; ox++) {
       int c0, c1; float v0, v1; bil_coef_exact(ox, IW, OW, c0, c1, v0, v1);
-      float wx = (c0 == ix ? v0 : 0.f) + (c1 == ix ? v1 : 0.f);
+      float wx = bil_weight_on(ix, c0, c1, v0, v1);
       if (wx == 0.f) continue;
       float d[8]; load8<T>(dy + (((long)b * OH + oy) * OW + ox) * C + c, d);
       float wgt = wy * wx;
@@ -507,7 +494,7 @@ __global__ void __launch_bounds__(256) avgpool_part_kernel(const T* __restrict__
 #pragma unroll
     for (int e = 0; e < 8; e++) s[0][e] += v[e];
   }
-  rowphase_reduce<1>(s, red, t, cg);
+  phase_reduce<1>(s, red, t, cg, rows);
   if (t < cg) {
     float* dst = part + ((long)b * gridDim.x + blockIdx.x) * C + c;
 #pragma unroll
@@ -594,26 +581,13 @@ __global__ void __launch_bounds__(128 * NM) mask_heads_bwd_kernel(const float* _
     for (int e = 0; e < 8; e++) ab[e] += o[e];
     adb += dl;
   }
-  // reduce over the 32 pixel rows: aw -> dw2, ab -> db1, adb (chunks 0,4,8,..) -> db2
-  float* r = red;
+  // phase reduction over the 32 pixel rows, one column per thread: aw -> dw2, ab -> db1, adb (element 0 of chunks
+  // 0, 4, 8, ..: column 32 k) -> db2
+  const float ad[8] = {adb, 0, 0, 0, 0, 0, 0, 0};
   for (int pass = 0; pass < 3; pass++) {
-    __syncthreads();
-    if (pass == 0) { for (int e = 0; e < 8; e++) r[t * 8 + e] = aw[e]; }
-    else if (pass == 1) { for (int e = 0; e < 8; e++) r[t * 8 + e] = ab[e]; }
-    else r[t * 8] = adb;
-    __syncthreads();
-    if (t < C) {
-      const int jj = t >> 3, e = t & 7;
-      if (pass < 2) {
-        float s = 0.f;
-        for (int q = 0; q < 32; q++) s += r[((q * NC) + jj) * 8 + e];
-        atomicAdd((pass == 0 ? dw2 : db1) + t, s);
-      } else if (t < NM) {
-        float s = 0.f;
-        for (int q = 0; q < 32; q++) s += r[((q * NC) + 4 * t) * 8];
-        atomicAdd(db2 + t, s);
-      }
-    }
+    phase_put(pass == 0 ? aw : pass == 1 ? ab : ad, red, t);
+    if (pass < 2) { if (t < C) atomicAdd((pass == 0 ? dw2 : db1) + t, phase_col<32>(red, t, NC)); }
+    else if (t < NM) atomicAdd(db2 + t, phase_col<32>(red, 32 * t, NC));
   }
 }
 
@@ -762,12 +736,13 @@ int s3od_mask_heads_bwd(int dtype, const float* dlogits, const void* hsave, cons
   long M = (long)B * HW;
   const int nb = (int)min(1024L, (M + 31) / 32);
   DISPATCH_T(dtype, {
-    if (NM == 3)
-      hipLaunchKernelGGL((mask_heads_bwd_kernel<T, 3>), dim3(nb), dim3(384), 0, (hipStream_t)stream, dlogits, (const T*)hsave, w2,
+    auto go = [&](auto heads) {
+      constexpr int N = decltype(heads)::value;
+      hipLaunchKernelGGL((mask_heads_bwd_kernel<T, N>), dim3(nb), dim3(128 * N), 0, (hipStream_t)stream, dlogits, (const T*)hsave, w2,
                          (T*)dh, dw2, db2, db1, M, HW);
-    else
-      hipLaunchKernelGGL((mask_heads_bwd_kernel<T, 1>), dim3(nb), dim3(128), 0, (hipStream_t)stream, dlogits, (const T*)hsave, w2,
-                         (T*)dh, dw2, db2, db1, M, HW);
+    };
+    if (NM == 3) go(std::integral_constant<int, 3>{});
+    else go(std::integral_constant<int, 1>{});
   });
   return s3od_check_launch("mask_heads_bwd");
 }

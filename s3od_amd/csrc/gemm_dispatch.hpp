@@ -1,17 +1,10 @@
-// What the GEMM entry files (linear_ops.hip, conv_ops.hip) share on the host side: the dtype dispatch, the tile
+// What the GEMM entry files (linear_ops.hip, conv_ops.hip) share on the host side: the tile
 // configurations, the split-K model and the kernels that fold split-K partials into dW.
 #pragma once
 #include "gemm.hpp"
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
-
-#define DISPATCH_T(dtype, ...)                                                  \
-  do {                                                                          \
-    if ((dtype) == S3OD_BF16) { typedef bf16 T; __VA_ARGS__ }                   \
-    else if ((dtype) == S3OD_F32) { typedef float T; __VA_ARGS__ }              \
-    else { s3od_set_error("bad dtype %d", (int)(dtype)); return 22; }           \
-  } while (0)
 
 static RowMap dense_rm() { RowMap r{}; r.mode = 0; return r; }
 

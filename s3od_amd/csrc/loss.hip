@@ -162,45 +162,61 @@ DEV float ssim_px(float mu1, float mu2, float e11, float e22, float e12, float* 
   return m;
 }
 
+// The tile pipeline both SSIM kernels run, by 256 threads over LDS arrays given by their base pointers:
+// ssim_stage: p = sigmoid(logits) and t over the E x E window with origin (y0, x0), zero outside the image -> xp, xt [E][E]
+template <int E> DEV void ssim_stage(const float* __restrict__ lg, const float* __restrict__ tg, int y0, int x0, int H, int W,
+                                     float* xp, float* xt, int tid) {
+  for (int i = tid; i < E * E; i += 256) {
+    int r = i / E, c = i - r * E, y = y0 + r, x = x0 + c;
+    bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
+    xp[i] = in ? 1.f / (1.f + __expf(-lg[(long)y * W + x])) : 0.f;
+    xt[i] = in ? tg[(long)y * W + x] : 0.f;
+  }
+}
+// ssim_rows5: the 11-tap row filter of p, t, pp, tt, pt over ROWS rows of xp, xt [ROWS][IC] -> hm [5][ROWS][OC] (OC = IC - 10)
+template <int ROWS, int IC, int OC> DEV void ssim_rows5(const float* xp, const float* xt, float* hm, const Gauss11& G, int tid) {
+  for (int i = tid; i < ROWS * OC; i += 256) {
+    int r = i / OC, c = i - r * OC;
+    float a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
+#pragma unroll
+    for (int k = 0; k < 11; k++) {
+      float p = xp[r * IC + c + k], t = xt[r * IC + c + k], g = G.g[k];
+      a0 += g * p; a1 += g * t; a2 += g * (p * p); a3 += g * (t * t); a4 += g * (p * t);
+    }
+    hm[(0 * ROWS + r) * OC + c] = a0; hm[(1 * ROWS + r) * OC + c] = a1; hm[(2 * ROWS + r) * OC + c] = a2;
+    hm[(3 * ROWS + r) * OC + c] = a3; hm[(4 * ROWS + r) * OC + c] = a4;
+  }
+}
+// ssim_col: the 11-tap column filter of NMAPS row-filtered maps hm [NMAPS][ROWS][OC] at output pixel (r, c) -> v
+template <int NMAPS, int ROWS, int OC> DEV void ssim_col(const float* hm, int r, int c, const Gauss11& G, float* v) {
+#pragma unroll
+  for (int q = 0; q < NMAPS; q++) v[q] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 11; k++) {
+    float g = G.g[k];
+#pragma unroll
+    for (int q = 0; q < NMAPS; q++) v[q] += g * hm[(q * ROWS + r + k) * OC + c];
+  }
+}
+
 // per (b,m) map: sums[bm*NS + 7] += sum over the tile of ssim_map(p = sigmoid(logits), t)
 __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__ logits, const float* __restrict__ tgt,
                                                        double* __restrict__ sums, int M, int H, int W, Gauss11 G) {
   constexpr int R = 5, E = ST + 2 * R;                     // 42
-  __shared__ float xp[E][E], xt[E][E];
-  __shared__ float hm[5][E][ST];                            // row-filtered p, t, pp, tt, pt
+  __shared__ float xp[E * E], xt[E * E];
+  __shared__ float hm[5 * E * ST];                          // row-filtered p, t, pp, tt, pt
   const int bm = blockIdx.z, b = bm / M, tid = threadIdx.x;
   const int y0 = blockIdx.y * ST - R, x0 = blockIdx.x * ST - R;
-  const float* lg = logits + (long)bm * H * W;
-  const float* tg = tgt + (long)b * H * W;
-  for (int i = tid; i < E * E; i += 256) {
-    int r = i / E, c = i - r * E, y = y0 + r, x = x0 + c;
-    bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    xp[r][c] = in ? 1.f / (1.f + __expf(-lg[(long)y * W + x])) : 0.f;
-    xt[r][c] = in ? tg[(long)y * W + x] : 0.f;
-  }
+  ssim_stage<E>(logits + (long)bm * H * W, tgt + (long)b * H * W, y0, x0, H, W, xp, xt, tid);
   __syncthreads();
-  for (int i = tid; i < E * ST; i += 256) {
-    int r = i / ST, c = i - r * ST;
-    float a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-      float p = xp[r][c + k], t = xt[r][c + k], g = G.g[k];
-      a0 += g * p; a1 += g * t; a2 += g * (p * p); a3 += g * (t * t); a4 += g * (p * t);
-    }
-    hm[0][r][c] = a0; hm[1][r][c] = a1; hm[2][r][c] = a2; hm[3][r][c] = a3; hm[4][r][c] = a4;
-  }
+  ssim_rows5<E, E, ST>(xp, xt, hm, G, tid);
   __syncthreads();
   float acc = 0.f;
   for (int i = tid; i < ST * ST; i += 256) {
     int r = i / ST, c = i - r * ST, y = y0 + R + r, x = x0 + R + c;
     if (y >= H || x >= W) continue;
-    float v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-      float g = G.g[k];
-#pragma unroll
-      for (int q = 0; q < 5; q++) v[q] += g * hm[q][r + k][c];
-    }
+    float v[5];
+    ssim_col<5, E, ST>(hm, r, c, G, v);
     acc += ssim_px(v[0], v[1], v[2], v[3], v[4], nullptr, nullptr, nullptr);
   }
   __shared__ float red[4];
@@ -230,38 +246,16 @@ __global__ void __launch_bounds__(256) ssim_grad_kernel(const float* __restrict_
   const long HW = (long)H * W;
   const int ty = blockIdx.y * ST, tx = blockIdx.x * ST;
   const int y1 = ty - 2 * R, x1 = tx - 2 * R;               // origin of the input halo
-  const float* lg = logits + (long)bm * HW;
-  const float* tg = tgt + (long)b * HW;
-  for (int i = tid; i < E1 * E1; i += 256) {
-    int r = i / E1, c = i - r * E1, y = y1 + r, x = x1 + c;
-    bool in = (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-    xp[i] = in ? 1.f / (1.f + __expf(-lg[(long)y * W + x])) : 0.f;
-    xt[i] = in ? tg[(long)y * W + x] : 0.f;
-  }
+  ssim_stage<E1>(logits + (long)bm * HW, tgt + (long)b * HW, y1, x1, H, W, xp, xt, tid);
   __syncthreads();
-  for (int i = tid; i < E1 * E2; i += 256) {                // rows of the halo, columns of the D region
-    int r = i / E2, c = i - r * E2;
-    float a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-      float p = xp[r * E1 + c + k], t = xt[r * E1 + c + k], g = G.g[k];
-      a0 += g * p; a1 += g * t; a2 += g * (p * p); a3 += g * (t * t); a4 += g * (p * t);
-    }
-    h1[(0 * E1 + r) * E2 + c] = a0; h1[(1 * E1 + r) * E2 + c] = a1; h1[(2 * E1 + r) * E2 + c] = a2;
-    h1[(3 * E1 + r) * E2 + c] = a3; h1[(4 * E1 + r) * E2 + c] = a4;
-  }
+  ssim_rows5<E1, E1, E2>(xp, xt, h1, G, tid);               // rows of the halo, columns of the D region
   __syncthreads();
   for (int i = tid; i < E2 * E2; i += 256) {                // D maps on the tile + halo 5
     int r = i / E2, c = i - r * E2, y = ty - R + r, x = tx - R + c;
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
     if ((unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W) {
-      float v[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-      for (int k = 0; k < 11; k++) {
-        float g = G.g[k];
-#pragma unroll
-        for (int q = 0; q < 5; q++) v[q] += g * h1[(q * E1 + r + k) * E2 + c];
-      }
+      float v[5];
+      ssim_col<5, E1, E2>(h1, r, c, G, v);
       ssim_px(v[0], v[1], v[2], v[3], v[4], &d0, &d1, &d2);
     }
     dm[(0 * E2 + r) * E2 + c] = d0; dm[(1 * E2 + r) * E2 + c] = d1; dm[(2 * E2 + r) * E2 + c] = d2;
@@ -282,14 +276,10 @@ __global__ void __launch_bounds__(256) ssim_grad_kernel(const float* __restrict_
   for (int i = tid; i < ST * ST; i += 256) {
     int r = i / ST, c = i - r * ST, y = ty + r, x = tx + c;
     if (y >= H || x >= W) continue;
-    float a0 = 0, a1 = 0, a2 = 0;
-#pragma unroll
-    for (int k = 0; k < 11; k++) {
-      float g = G.g[k];
-      a0 += g * h2[(0 * E2 + r + k) * ST + c]; a1 += g * h2[(1 * E2 + r + k) * ST + c]; a2 += g * h2[(2 * E2 + r + k) * ST + c];
-    }
+    float a[3];
+    ssim_col<3, E2, ST>(h2, r, c, G, a);
     float p = xp[(r + 2 * R) * E1 + c + 2 * R], t = xt[(r + 2 * R) * E1 + c + 2 * R];
-    float dp = a0 + 2.f * p * a1 + t * a2;
+    float dp = a[0] + 2.f * p * a[1] + t * a[2];
     dlogits[(long)bm * HW + (long)y * W + x] += gs * dp * p * (1.f - p);
   }
 }

@@ -1,14 +1,8 @@
 // Memory-bound ViT kernels: patch im2col, token prefix, RoPE table, LayerNorm fwd/bwd,
 // tap cast, bias / LayerScale gradient reductions, QKV-gradient RoPE inverse.
 // DINOv3 arithmetic follows tf:models/dinov3_vit/modeling_dinov3_vit.py (transformers).
-#include "common.hpp"
-
-#define DISPATCH_T(dtype, ...)                                                  \
-  do {                                                                          \
-    if ((dtype) == S3OD_BF16) { typedef bf16 T; __VA_ARGS__ }                   \
-    else if ((dtype) == S3OD_F32) { typedef float T; __VA_ARGS__ }              \
-    else { s3od_set_error("bad dtype %d", (int)(dtype)); return 22; }           \
-  } while (0)
+#include "reduce.hpp"
+#include <type_traits>
 
 // ---------------------------------------------------------------- patch embed im2col
 // x: [B,3,H,W] f32 NCHW -> cols [B*P, 768] T, k = c*256 + kh*16 + kw (conv weight flatten order)
@@ -77,7 +71,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
   const float* xr = x + (long)row * D;
   float v[4 * NV];
 #pragma unroll
-  for (int i = 0; i < NV; i++) { float4 f = ((const float4*)xr)[lane + 64 * i]; v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w; }
+  for (int i = 0; i < NV; i++) load4<float>(xr + 4 * (lane + 64 * i), v + 4 * i);
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < 4 * NV; i++) s += v[i];
@@ -88,16 +82,16 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const float* __restrict__ x
   float var = warp_sum(q) * (1.0f / D);
   float rstd = 1.0f / sqrtf(var + eps);
   if (y) {                                         // y == nullptr: statistics only
-  T* yr = y + (long)row * D;
+    T* yr = y + (long)row * D;
 #pragma unroll
-  for (int i = 0; i < NV; i++) {
-    int c = 4 * (lane + 64 * i);
-    float4 wf = *(const float4*)(w + c), bf = *(const float4*)(b + c);
-    float o0 = (v[4 * i] - mean) * rstd * wf.x + bf.x, o1 = (v[4 * i + 1] - mean) * rstd * wf.y + bf.y;
-    float o2 = (v[4 * i + 2] - mean) * rstd * wf.z + bf.z, o3 = (v[4 * i + 3] - mean) * rstd * wf.w + bf.w;
-    if constexpr (sizeof(T) == 4) *(float4*)(yr + c) = make_float4(o0, o1, o2, o3);
-    else { bf16x4 o = {(bf16)o0, (bf16)o1, (bf16)o2, (bf16)o3}; *(bf16x4*)(yr + c) = o; }
-  }
+    for (int i = 0; i < NV; i++) {
+      int c = 4 * (lane + 64 * i);
+      float wf[4], bf[4], o[4];
+      load4<float>(w + c, wf); load4<float>(b + c, bf);
+#pragma unroll
+      for (int e = 0; e < 4; e++) o[e] = (v[4 * i + e] - mean) * rstd * wf[e] + bf[e];
+      store4<T>(yr + c, o);
+    }
   }
   if (lane == 0) { mean_o[row] = mean; rstd_o[row] = rstd; }
 }
@@ -129,10 +123,7 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const T* __restrict__ dy, c
   for (int i = 0; i < NE; i++) { pw[i] = 0.f; pb[i] = 0.f; }
   if constexpr (LS) {
 #pragma unroll
-    for (int i = 0; i < NV; i++) {
-      const float4 l4 = *(const float4*)(lam + 4 * (lane + 64 * i));
-      lv[4 * i] = l4.x; lv[4 * i + 1] = l4.y; lv[4 * i + 2] = l4.z; lv[4 * i + 3] = l4.w;
-    }
+    for (int i = 0; i < NV; i++) load4<float>(lam + 4 * (lane + 64 * i), lv + 4 * i);
 #pragma unroll
     for (int i = 0; i < NE; i++) { pl[i] = 0.f; pd[i] = 0.f; }
   }
@@ -141,22 +132,19 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const T* __restrict__ dy, c
     const float* xr = x + (long)row * D;
     float mu = mean[row], rs = rstd[row];
     float xh[NE], g[NE], dyv[NE];
-    float4 rr4[NV];
+    float rr[NV][4];
     bf16x4 uu4[LS ? NV : 1];
 #pragma unroll
     for (int i = 0; i < NV; i++) {  // issue the residual-gradient (and LayerScale input) loads before the row reductions
-      rr4[i] = dres ? *(const float4*)(dres + (long)row * D + 4 * (lane + 64 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+      if (dres) load4<float>(dres + (long)row * D + 4 * (lane + 64 * i), rr[i]);
+      else rr[i][0] = rr[i][1] = rr[i][2] = rr[i][3] = 0.f;
       if constexpr (LS && sizeof(T) == 2) uu4[i] = *(const bf16x4*)(u + (long)row * D + 4 * (lane + 64 * i));
     }
 #pragma unroll
     for (int i = 0; i < NV; i++) {
       int c = 4 * (lane + 64 * i);
-      float4 xf = *(const float4*)(xr + c);
-      float4 wf = *(const float4*)(w + c);
-      float d4[4];
-      if constexpr (sizeof(T) == 4) { float4 t = *(const float4*)(dy + (long)row * D + c); d4[0] = t.x; d4[1] = t.y; d4[2] = t.z; d4[3] = t.w; }
-      else { bf16x4 t = *(const bf16x4*)(dy + (long)row * D + c); d4[0] = (float)t[0]; d4[1] = (float)t[1]; d4[2] = (float)t[2]; d4[3] = (float)t[3]; }
-      float xs[4] = {xf.x, xf.y, xf.z, xf.w}, wv[4] = {wf.x, wf.y, wf.z, wf.w};
+      float xs[4], wv[4], d4[4];
+      load4<float>(xr + c, xs); load4<float>(w + c, wv); load4<T>(dy + (long)row * D + c, d4);
 #pragma unroll
       for (int e = 0; e < 4; e++) { xh[4 * i + e] = (xs[e] - mu) * rs; dyv[4 * i + e] = d4[e]; g[4 * i + e] = d4[e] * wv[e]; }
     }
@@ -169,21 +157,18 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const T* __restrict__ dy, c
     for (int i = 0; i < NV; i++) {
       int c = 4 * (lane + 64 * i);
       float o[4];
-      float rr[4] = {rr4[i].x, rr4[i].y, rr4[i].z, rr4[i].w};
 #pragma unroll
       for (int e = 0; e < 4; e++) {
         int k = 4 * i + e;
-        o[e] = rr[e] + rs * (g[k] - s1 - xh[k] * s2);
+        o[e] = rr[i][e] + rs * (g[k] - s1 - xh[k] * s2);
         pw[k] += dyv[k] * xh[k];
         pb[k] += dyv[k];
       }
-      *(float4*)(dx + (long)row * D + c) = make_float4(o[0], o[1], o[2], o[3]);
+      store4<float>(dx + (long)row * D + c, o);
       if constexpr (LS) {
         float uv[4];
-        if constexpr (sizeof(T) == 4) {
-          const float4 t = *(const float4*)(u + (long)row * D + c);
-          uv[0] = t.x; uv[1] = t.y; uv[2] = t.z; uv[3] = t.w;
-        } else {
+        if constexpr (sizeof(T) == 4) load4<T>(u + (long)row * D + c, uv);
+        else {
 #pragma unroll
           for (int e = 0; e < 4; e++) uv[e] = (float)uu4[i][e];
         }
@@ -218,23 +203,12 @@ __global__ void __launch_bounds__(256) ln_bwd_kernel(const T* __restrict__ dy, c
       }
   }
   __syncthreads();
-  float* rep = ws + (long)(blockIdx.x % S3OD_NREP) * 2 * D;   // replicated [dw | db] partials
+  float* rep = replica(ws, blockIdx.x, 2, D);   // replicated [dw | db] partials
   for (int i = threadIdx.x; i < D; i += 256) { atomicAdd(rep + i, sdw[i]); atomicAdd(rep + D + i, sdb[i]); }
   if constexpr (LS) {
-    float* rep2 = ws2 + (long)(blockIdx.x % S3OD_NREP) * 2 * D;   // replicated [dlam | dbias] partials
+    float* rep2 = replica(ws2, blockIdx.x, 2, D);   // replicated [dlam | dbias] partials
     for (int i = threadIdx.x; i < D; i += 256) { atomicAdd(rep2 + i, sred[2][i]); atomicAdd(rep2 + D + i, sred[3][i]); }
   }
-}
-
-// a[i] += sum_r ws[r][i], b[i] += sum_r ws[r][D + i]   (fold of the replicated 2 x D partials; a/b may be null)
-// sums the S3OD_NREP replicas of [a | b] partials and clears them (the workspace enters and leaves all zero)
-__global__ void fold2_kernel(float* __restrict__ ws, float* __restrict__ a, float* __restrict__ b, int D) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 2 * D) return;
-  float s = 0.f;
-  for (int r = 0; r < S3OD_NREP; r++) { s += ws[(long)r * 2 * D + i]; ws[(long)r * 2 * D + i] = 0.f; }
-  if (i < D) { if (a) a[i] += s; }
-  else if (b) b[i - D] += s;
 }
 
 // taps: x f32 [B, Ntok, D] -> T [B, P, D] (drop 1 + 4 prefix tokens; src/s3od/model.py:75-84)
@@ -251,8 +225,8 @@ __global__ void cast_tap_kernel(const float* __restrict__ x, T* __restrict__ y, 
 }
 
 // column sums of a [M, N] T matrix (bias gradients): out[n] += sum_m a[m, n]
-// block = 256 threads = tpr column-groups (8 columns each) x rp row phases; LDS reduction over
-// the row phases, then per block either one fp32 atomic per column (part == nullptr) or the block's partial
+// block = 256 threads = tpr column-groups (8 columns each) x rp row phases; phase reduction in LDS
+// (reduce.hpp), then per block either one fp32 atomic per column (part == nullptr) or the block's partial
 // sums stored to part[blockIdx.y][N] for colsum_fold_kernel.
 template <typename T>
 __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ a, long lda, int M, int N, float* __restrict__ out,
@@ -281,13 +255,9 @@ __global__ void __launch_bounds__(256) colsum_kernel(const T* __restrict__ a, lo
       for (int e = 0; e < 8; e++) s[e] += v[e];
     }
   }
-#pragma unroll
-  for (int e = 0; e < 8; e++) red[t * 8 + e] = s[e];
-  __syncthreads();
+  phase_put(s, red, t, /*fresh=*/true);
   if (ph == 0 && cg < G) {
-    for (int q = 1; q < rp; q++)
-#pragma unroll
-      for (int e = 0; e < 8; e++) s[e] += red[(q * tpr + ci) * 8 + e];
+    phase_sum8(s, red, ci, tpr, rp);
     if (part) {
       float* pr = part + (long)blockIdx.y * N + cg * 8;
       *(float4*)pr = make_float4(s[0], s[1], s[2], s[3]);
@@ -326,7 +296,8 @@ __global__ void __launch_bounds__(256) colsum_fold_kernel(const float* __restric
 }
 
 // LayerScale backward: du = dx * lam (T); dlam[n] += sum_m dx*u ; dbias[n] += sum_m du
-// block = 4 * D/8 threads = D/8 column groups (8 columns) x 4 row phases; LDS reduction, 2 x D atomics per block
+// block = 4 * D/8 threads = D/8 column groups (8 columns) x 4 row phases; phase reduction in LDS with every thread
+// taking columns (phase_col), 2 x D atomics per block
 template <typename T, int D>
 __global__ void __launch_bounds__(D / 2) scale_bwd_kernel(const float* __restrict__ dx, const T* __restrict__ u, const float* __restrict__ lam,
                                  T* __restrict__ du, float* __restrict__ ws, int M, int rows_per_block) {
@@ -346,18 +317,10 @@ __global__ void __launch_bounds__(D / 2) scale_bwd_kernel(const float* __restric
     for (int e = 0; e < 8; e++) { o[e] = d[e] * l[e]; sl[e] += d[e] * uu[e]; sb[e] += o[e]; }
     store8<T>(du + (long)r * D + n, o);
   }
+  float* rep = replica(ws, blockIdx.x, 2, D);   // replicated [dlam | dbias] partials
   for (int pass = 0; pass < 2; pass++) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; e++) red[t * 8 + e] = pass ? sb[e] : sl[e];
-    __syncthreads();
-    for (int c = t; c < D; c += NT) {
-      const int gg = c >> 3, e = c & 7;
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; q++) s += red[(q * NG + gg) * 8 + e];
-      atomicAdd(ws + (long)(blockIdx.x % S3OD_NREP) * 2 * D + (pass ? D : 0) + c, s);
-    }
+    phase_put(pass ? sb : sl, red, t);
+    for (int c = t; c < D; c += NT) atomicAdd(rep + (pass ? D : 0) + c, phase_col<4>(red, c, NG));
   }
 }
 
@@ -412,7 +375,7 @@ __global__ void __launch_bounds__(24 * H) qkv_unrope_kernel(const T* __restrict_
     }
   }
   if (which != 1 && ws) {   // replicated partials: ws[blk % NREP][q D | v D]
-    float* dst = ws + (long)(blockIdx.x % S3OD_NREP) * 2 * D + (which == 0 ? 0 : D) + h * 64 + d0;
+    float* dst = replica(ws, blockIdx.x, 2, D) + (which == 0 ? 0 : D) + h * 64 + d0;
 #pragma unroll
     for (int e = 0; e < 8; e++) atomicAdd(dst + e, acc[e]);
   }
@@ -475,7 +438,7 @@ int s3od_layernorm_bwd(int dtype, const void* dy, const float* x, const float* m
       hipLaunchKernelGGL((ln_bwd_kernel<T, D>), dim3(cdiv(M, rpb)), dim3(256), 0, st, (const T*)dy, x, mean, rstd, w, dres, dx, ws, M, rpb);
     });
   });
-  hipLaunchKernelGGL(fold2_kernel, dim3(cdiv(2 * D_, 256)), dim3(256), 0, st, ws, dw, db, D_);
+  replica_fold2(ws, dw, db, D_, st);
   return s3od_check_launch("layernorm_bwd");
 }
 
@@ -496,8 +459,8 @@ int s3od_layernorm_ls_bwd(int dtype, const void* dy, const float* x, const float
                          dx, ws, M, rpb, (const T*)u, lam, (T*)du, ws2);
     });
   });
-  hipLaunchKernelGGL(fold2_kernel, dim3(cdiv(2 * D_, 256)), dim3(256), 0, st, ws, dw, db, D_);
-  hipLaunchKernelGGL(fold2_kernel, dim3(cdiv(2 * D_, 256)), dim3(256), 0, st, ws2, dlam, dbias, D_);
+  replica_fold2(ws, dw, db, D_, st);
+  replica_fold2(ws2, dlam, dbias, D_, st);
   return s3od_check_launch("layernorm_ls_bwd");
 }
 
@@ -514,12 +477,12 @@ int s3od_cast_tap(int dtype, const float* x, void* y, int B, int Ntok, int P, in
 // atomics, which serialise on one address in L2: 256 / 512 / 1024 of them cost ~50 / 100 / 200 us whatever the
 // matrix size (tools/colsum_bench.py, profiles/r05w_colsum.txt); with one, the blocks store partial rows and a
 // second pass adds them in a fixed order
-static long colsum_rpb(int M, int gx, bool ws) { (void)ws; return max(64L, (long)M * gx / 512); }
+static long colsum_rpb(int M, int gx) { return max(64L, (long)M * gx / 512); }
 // bytes of the partial-sum workspace s3od_colsum uses for these arguments
 int s3od_colsum_ws(int M, int N, long* bytes) {
   S3OD_REQUIRE(bytes != nullptr && N % 8 == 0, "colsum_ws: bad arguments");
   const int G = N / 8, tpr = G < 256 ? G : 256, gx = cdiv(G, tpr);
-  *bytes = 4L * cdiv(M, colsum_rpb(M, gx, true)) * N;
+  *bytes = 4L * cdiv(M, colsum_rpb(M, gx)) * N;
   return 0;
 }
 
@@ -529,7 +492,7 @@ int s3od_colsum(int dtype, const void* a, long lda, int M, int N, float* out, fl
   long need = 0;
   if (ws) s3od_colsum_ws(M, N, &need);
   const bool two_pass = ws && ws_bytes >= need && N % 4 == 0 && !S3OD_OFF("S3OD_COLSUM_2P");
-  const long rpb = colsum_rpb(M, gx, two_pass);
+  const long rpb = colsum_rpb(M, gx);
   const int nb = (int)cdiv(M, rpb);
   dim3 grid(gx, nb);
   DISPATCH_T(dtype, {
@@ -550,7 +513,7 @@ int s3od_layerscale_bwd(int dtype, const float* dx, const void* u, const float* 
       hipLaunchKernelGGL((scale_bwd_kernel<T, D>), dim3(cdiv(M, rpb)), dim3(D / 2), 0, st, dx, (const T*)u, lam, (T*)du, ws, M, rpb);
     });
   });
-  hipLaunchKernelGGL(fold2_kernel, dim3(cdiv(2 * D_, 256)), dim3(256), 0, st, ws, dlam, dbias, D_);
+  replica_fold2(ws, dlam, dbias, D_, st);
   return s3od_check_launch("layerscale_bwd");
 }
 
@@ -564,14 +527,15 @@ int s3od_qkv_unrope(int dtype, const void* dq, const void* dk, const void* dv, c
   const int rpb = S3OD_KNOB("S3OD_UNROPE_RPB", 64);
   hipStream_t st = (hipStream_t)stream;
   DISPATCH_T(dtype, {
-    if (H == 12)
-      hipLaunchKernelGGL((qkv_unrope_kernel<T, 12>), dim3(cdiv(M, rpb)), dim3(24 * 12), 0, st, (const T*)dq, (const T*)dk,
+    auto go = [&](auto heads) {
+      constexpr int NH = decltype(heads)::value;
+      hipLaunchKernelGGL((qkv_unrope_kernel<T, NH>), dim3(cdiv(M, rpb)), dim3(24 * NH), 0, st, (const T*)dq, (const T*)dk,
                          (const T*)dv, cs, sn, (T*)dqkv, ws, B, Ntok, P, rpb);
-    else
-      hipLaunchKernelGGL((qkv_unrope_kernel<T, 16>), dim3(cdiv(M, rpb)), dim3(24 * 16), 0, st, (const T*)dq, (const T*)dk,
-                         (const T*)dv, cs, sn, (T*)dqkv, ws, B, Ntok, P, rpb);
+    };
+    if (H == 12) go(std::integral_constant<int, 12>{});
+    else go(std::integral_constant<int, 16>{});
   });
-  if (ws) hipLaunchKernelGGL(fold2_kernel, dim3(cdiv(2 * D_, 256)), dim3(256), 0, st, ws, dbq, dbv, D_);
+  if (ws) replica_fold2(ws, dbq, dbv, D_, st);
   return s3od_check_launch("qkv_unrope");
 }
 

@@ -384,10 +384,13 @@ def test_attn_bwd_qkv_vs_reference(N, P, dt):
 
 
 @pytest.mark.parametrize("dt", DTYPES)
-@pytest.mark.parametrize("N,P", QKV_SHAPES)
-def test_attn_bwd_then_qkv_unrope_vs_reference(N, P, dt):
-    """s3od_attn_bwd + s3od_qkv_unrope against the same reference (H = 12: s3od_qkv_unrope is built for 12 / 16)"""
-    _qkv_case(dt, N, P, 12, fused=False)
+@pytest.mark.parametrize("N,P,Hh", [pytest.param(n, p, 12, id=f"{n}-{p}") for n, p in QKV_SHAPES]
+                         + [pytest.param(69, 64, 16, id="69-64-H16")])
+def test_attn_bwd_then_qkv_unrope_vs_reference(N, P, Hh, dt):
+    """s3od_attn_bwd + s3od_qkv_unrope against the same reference (s3od_qkv_unrope is built for H = 12 / 16: the
+    shapes at 12 heads, and one at 16, the other instance, which nothing else runs; B*N = 138 rows there and in
+    69-64 is no multiple of the 4 rows the kernel loads together)"""
+    _qkv_case(dt, N, P, Hh, fused=False)
 
 
 # ================================================================================================ 5: untested branches

@@ -24,7 +24,6 @@ EXPECTED = [
     r"^attn_bwd_dq_kernel\(float const\*",
     r"^_Z22attn_bwd_dkdv32_kernelILi4EE",
     r"^_Z20attn_bwd_dq32_kernelILi4EE",
-    r"^\(anonymous namespace\)::qkv_fold_kernel\(",
 ]
 
 
@@ -34,7 +33,7 @@ def attn_kernels():
         pytest.skip("objcopy / clang-offload-bundler / llvm-readelf / c++filt not available")
     if not list((ROOT / "build").glob("*.o")):
         pytest.skip("build/*.o absent: run make (or __graft_entry__.build()) first")
-    k = {n: v for n, v in _kernels().items() if re.search(r"attn_|qkv_fold", n[0])}
+    k = {n: v for n, v in _kernels().items() if re.search(r"attn_", n[0])}     # (the bias-sum fold is reduce.hpp's, shared with vit_ops.hip)
     assert k, "no attention kernel found in build/*.o"
     return k
 

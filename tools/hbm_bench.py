@@ -46,7 +46,7 @@ def unrope(B=16, N=4101):
     out = torch.empty(B * N, 2304, device="cuda", dtype=torch.bfloat16)
     bq, bv = torch.zeros(768, device="cuda"), torch.zeros(768, device="cuda")
     ws = torch.zeros(32 * 1536, device="cuda")
-    f = lambda: lib()("s3od_qkv_unrope", BF16, dq, dk, dv, cs, sn, out, bq, bv, ws, B, N, N - 5, stream())
+    f = lambda: lib()("s3od_qkv_unrope", BF16, dq, dk, dv, cs, sn, out, bq, bv, ws, B, N, N - 5, 12, stream())
     t = timeit(f)
     nbytes = 2 * out.numel() * 2
     print(f"qkv_unrope B={B} N={N}: {t * 1e6:8.1f} us  {nbytes / t / 1e12:6.2f} TB/s")

@@ -8,7 +8,12 @@ A path may carry knobs, "path@S3OD_GEMM_CFG=6,S3OD_X=1": they are set in the env
 build (S3OD_AB=1, set here, makes the library read them per call), so one build can be A/B'd against itself.
 
 Workloads: attn (s3od_attn_fwd + s3od_attn_bwd_qkv at the training shape bs 16 N 4101 and the C5 shape bs 4 N 16389);
-lin (the ViT linears of the bs-16 1024^2 step with their real epilogues, the 256-channel 3x3 conv; tools/lin_sweep.py shapes).
+lin (the ViT linears of the bs-16 1024^2 step with their real epilogues, the 256-channel 3x3 conv; tools/lin_sweep.py shapes);
+glue (every entry point of decoder_ops.hip / vit_ops.hip / loss.hip that reduces, folds, resizes or repacks, at edge
+shapes and at the training step's shapes: give the first build twice, `glue parent parent new`, and each output of the
+third is judged by whether the first two agree bit for bit -- then it must too -- or only to summation order, as the sums
+through fp32 atomics do -- then rel-L2 1e-5, or the first two's own scatter where that is larger; the training
+shapes are also timed).
 """
 import ctypes
 import os
@@ -174,6 +179,237 @@ def lin(libs, rounds):
         print(line, "| rel vs lib0", " ".join(f"{e:.1e}" for e in errs), flush=True)
 
 
+def glue(libs, rounds):
+    """Each case: name, timed?, factory taking a library -> (call, {output name: tensor}) on shared seeded inputs."""
+    F32 = 0
+    g = torch.Generator(device="cuda").manual_seed(0)
+    rn = lambda *s, dt=torch.float32: torch.randn(*s, device="cuda", generator=g).to(dt)
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, device="cuda", dtype=dt)
+    e = lambda *s, dt=torch.float32: torch.empty(*s, device="cuda", dtype=dt)
+    st = stream()
+    tdt = lambda code: torch.bfloat16 if code == BF16 else torch.float32
+    cases = []
+
+    def bn(code, C, npix, relu, dcb, timed=False):
+        dy, zz, y = rn(npix, C, dt=tdt(code)), rn(npix, C, dt=tdt(code)), rn(npix, C, dt=tdt(code))
+        mean, rstd, w = rn(C) * 0.1, torch.rand(C, device="cuda", generator=g) + 0.5, rn(C)
+        sc, sh = (w * rstd).contiguous(), rn(C) * 0.3
+
+        def mk(L):
+            o = {"dz": e(npix, C, dt=tdt(code)), "dw": z(C), "db": z(C), "sums": z(NREP * 3 * C, dt=torch.float64)}
+            if dcb:
+                o["dcb"] = z(C)
+            if relu:
+                f = lambda: L("s3od_bn_relu_bwd", code, dy, zz, sc, sh, mean, rstd, w, o["sums"], o["dz"], o["dw"], o["db"],
+                              o.get("dcb"), npix, C, st)
+            else:
+                f = lambda: L("s3od_bn_bwd", code, dy, zz, y, mean, rstd, w, o["sums"], o["dz"], o["dw"], o["db"], o.get("dcb"),
+                              npix, C, st)
+            return f, o
+        cases.append((f"bn_{'relu_' if relu else ''}bwd dt{code} C{C} npix{npix} dcb{int(dcb)}", timed, mk))
+
+    def bn_fin(C, count):
+        stats0 = rn(NREP * 2 * C).double().abs() * count
+        w, b = rn(C), rn(C)
+
+        def mk(L):
+            o = {"stats": stats0.clone(), "rm": z(C), "rv": z(C) + 1, "mean": e(C), "rstd": e(C), "scale": e(C), "shift": e(C)}
+            def f():
+                o["stats"].copy_(stats0)
+                L("s3od_bn_finalize", o["stats"], count, w, b, o["rm"], o["rv"], 0.1, 1e-5, o["mean"], o["rstd"], o["scale"],
+                  o["shift"], C, st)
+            return f, o
+        cases.append((f"bn_finalize C{C}", C == 256, mk))
+
+    def ln(code, M, D, dres, timed=False):
+        x, w, b = rn(M, D), rn(D), rn(D)
+        mean, rstd = x.mean(1), torch.rsqrt(x.var(1, unbiased=False) + 1e-5)
+        dy, u, lam = rn(M, D, dt=tdt(code)), rn(M, D, dt=tdt(code)), torch.rand(D, device="cuda", generator=g) + 0.1
+        dr = rn(M, D) if dres else None
+
+        def fwd(L):
+            o = {"y": e(M, D, dt=tdt(code)), "mean": e(M), "rstd": e(M)}
+            return (lambda: L("s3od_layernorm_fwd", code, x, w, b, o["y"], o["mean"], o["rstd"], M, D, 1e-5, st)), o
+
+        def fused(L):
+            o = {"dx": e(M, D), "du": e(M, D, dt=tdt(code)), "dw": z(D), "db": z(D), "dlam": z(D), "dbias": z(D),
+                 "ws": z(NREP * 2 * D), "ws2": z(NREP * 2 * D)}
+            return (lambda: L("s3od_layernorm_ls_bwd", code, dy, x, mean, rstd, w, dr, o["dx"], o["dw"], o["db"], o["ws"], u, lam,
+                              o["du"], o["dlam"], o["dbias"], o["ws2"], M, D, st)), o
+
+        def pair(L):
+            o = {"dx": e(M, D), "du": e(M, D, dt=tdt(code)), "dw": z(D), "db": z(D), "dlam": z(D), "dbias": z(D),
+                 "ws": z(NREP * 2 * D), "ws2": z(NREP * 2 * D)}
+            def f():
+                L("s3od_layernorm_bwd", code, dy, x, mean, rstd, w, dr, o["dx"], o["dw"], o["db"], o["ws"], M, D, st)
+                L("s3od_layerscale_bwd", code, o["dx"], u, lam, o["du"], o["dlam"], o["dbias"], o["ws2"], M, D, st)
+            return f, o
+        tag = f"dt{code} M{M} D{D} dres{int(dres)}"
+        cases.extend([(f"layernorm_fwd {tag}", timed, fwd), (f"layernorm_ls_bwd {tag}", timed, fused),
+                      (f"layernorm_bwd + layerscale_bwd {tag}", timed, pair)])
+
+    def colsum(M, N, two_pass, timed=False):
+        a, base = rn(M, N, dt=torch.bfloat16), rn(N)
+        nb = ctypes.c_long(0)
+        libs[0]("s3od_colsum_ws", M, N, ctypes.addressof(nb))
+
+        def mk(L):
+            o = {"out": base.clone()}
+            ws = e(nb.value // 4) if two_pass else None
+            return (lambda: L("s3od_colsum", BF16, a, N, M, N, o["out"], ws, nb.value if two_pass else 0, st)), o
+        cases.append((f"colsum {'two' if two_pass else 'one'}-pass M{M} N{N}", timed, mk))
+
+    def unrope(code, B, N, P, H, timed=False):
+        dq, dk, dv = (rn(B * H, N, 64, dt=tdt(code)) for _ in range(3))
+        cs, sn = rn(max(P, 1), 64), rn(max(P, 1), 64)
+
+        def mk(L):
+            o = {"dqkv": e(B * N, 3 * H * 64, dt=tdt(code)), "dbq": z(H * 64), "dbv": z(H * 64), "ws": z(NREP * 2 * H * 64)}
+            return (lambda: L("s3od_qkv_unrope", code, dq, dk, dv, cs, sn, o["dqkv"], o["dbq"], o["dbv"], o["ws"], B, N, P, H, st)), o
+        cases.append((f"qkv_unrope dt{code} B{B} N{N} P{P} H{H}", timed, mk))
+
+    def bilinear(code, B, IH, IW, OH, OW, C, timed=False):
+        x, dy, bc = rn(B, IH, IW, C, dt=tdt(code)), rn(B, OH, OW, C, dt=tdt(code)), rn(B, C)
+
+        def fwd(L):
+            o = {"y": e(B, OH, OW, C, dt=tdt(code))}
+            return (lambda: L("s3od_bilinear_fwd", code, x, o["y"], B, IH, IW, OH, OW, C, st)), o
+
+        def bwd(L):
+            o = {"dx": e(B, IH, IW, C, dt=tdt(code))}
+            return (lambda: L("s3od_bilinear_bwd", code, dy, bc, o["dx"], B, IH, IW, OH, OW, C, st)), o
+        tag = f"dt{code} B{B} {IH}x{IW}->{OH}x{OW} C{C}"
+        cases.extend([(f"bilinear_fwd {tag}", timed, fwd), (f"bilinear_bwd {tag}", timed, bwd)])
+
+    def avgpool(code, B, HW, C, timed=False):
+        x = rn(B, HW, C, dt=tdt(code))
+
+        def mk(L):
+            o = {"out": e(B, C)}
+            ws = e(B * cdiv(HW, 1024) * C)
+            return (lambda: L("s3od_avgpool", code, x, o["out"], ws, B, HW, C, st)), o
+        cases.append((f"avgpool dt{code} B{B} HW{HW} C{C}", timed, mk))
+
+    def heads(code, B, HW, NM, timed=False):
+        dl, h, w2 = rn(B, NM, HW), rn(B * HW, 32 * NM, dt=tdt(code)), rn(NM, 32)
+
+        def mk(L):
+            o = {"dh": e(B * HW, 32 * NM, dt=tdt(code)), "dw2": z(NM, 32), "db2": z(NM), "db1": z(32 * NM)}
+            def f():
+                for k in ("dw2", "db2", "db1"):
+                    o[k].zero_()
+                L("s3od_mask_heads_bwd", code, dl, h, w2, o["dh"], o["dw2"], o["db2"], o["db1"], B, HW, NM, st)
+            return f, o
+        cases.append((f"mask_heads_bwd dt{code} B{B} HW{HW} NM{NM}", timed, mk))
+
+    def ssim(B, M, H, W, timed=False):
+        lg, tg, pi = rn(B, M, H, W), (rn(B, H, W) > 0).float(), rn(B, M)
+
+        def mk(L):
+            o = {"out": z(16 + B * M + B), "dlogits": e(B, M, H, W), "d_iou": e(B, M)}
+            sums, coef, iws, diu = z(B * M * 8, dt=torch.float64), e(B * M * 4), e(B * M * 2), e(B * M)
+            def f():
+                L("s3od_mask_loss_fwd", lg, tg, pi, B, M, H * W, W, 1.0, 1.0, 0.0, 1.0, 1.0, 0.05, 0.25, 2.0, sums, coef, iws, diu,
+                  o["out"], st)
+                L("s3od_mask_loss_bwd", lg, tg, coef, iws, diu, None, o["dlogits"], o["d_iou"], B, M, H * W, W, 1, 0.25, 2.0, st)
+            return f, o
+        cases.append((f"mask_loss fwd+bwd with SSIM B{B} M{M} {H}x{W}", timed, mk))
+
+    def repack(timed=False):
+        """the layouts of tests/test_gpu_repack.py plus the linears of one ViT layer"""
+        ents = [(rn(3072, 768), 0, 3072, 768, 1, 0, 0), (rn(768, 3072), 0, 768, 3072, 1, 0, 0), (rn(2304, 768), 0, 2304, 768, 1, 0, 0),
+                (rn(256, 128, 3, 3), 0, 256, 128, 9, 0, 0), (rn(64, 96, 3, 3), 32, 64, 96, 9, 1, 128),
+                (rn(128, 64, 4, 4), 0, 128, 64, 16, 2, 128), (rn(1 + 768 * 40)[1:], 1, 40, 768, 1, 0, 0)]
+        chunk = 16384
+
+        def mk(L):
+            o, rows, ct, co = {}, [], [], []
+            for t, (src, off, O, I, KHW, mode, ld) in enumerate(ents):
+                n = (I * KHW * ld if mode else O * I * KHW) + off
+                o[f"w{t}"] = z(n, dt=torch.bfloat16)
+                rows.append([src.data_ptr(), o[f"w{t}"].data_ptr(), O, I, KHW, off, mode, ld])
+                for c0 in range(0, O * I * KHW, chunk):
+                    ct.append(t); co.append(c0)
+            tab = torch.tensor(rows, dtype=torch.int64, device="cuda")
+            ctt, cot = torch.tensor(ct, dtype=torch.int32, device="cuda"), torch.tensor(co, dtype=torch.int64, device="cuda")
+            o["_keep"] = tab                     # (the tables must outlive the launches)
+            return (lambda: L("s3od_repack_multi", BF16, tab, ctt, cot, len(ct), chunk, st)), o
+        cases.append(("repack_multi", timed, mk))
+
+    cdiv = lambda a, b: (a + b - 1) // b
+    # ---- the edge shapes of tests/test_gpu_bn_relu.py, test_gpu_vit_ops.py, test_gpu_colsum.py
+    for code in (F32, BF16):
+        for C in (8, 64, 256, 2048):
+            rows = 256 // (C // 8)
+            for npix in dict.fromkeys((1, rows - 1, 4 * rows + 1, 3017)):
+                if npix > 0:
+                    bn(code, C, npix, relu=npix % 2 == 1, dcb=C != 64)
+        for M in (1, 3, 5, 33, 65, 8202):
+            for D in (768, 1024):
+                ln(code, M, D, dres=M != 33)
+        unrope(code, 2, 69, 64, 12); unrope(code, 2, 69, 64, 16); unrope(code, 2, 5, 0, 12)
+        bilinear(code, 2, 12, 9, 25, 20, 16); bilinear(code, 2, 7, 5, 14, 10, 8)
+        avgpool(code, 2, 1500, 256); avgpool(code, 8, 37, 64)
+        heads(code, 2, 1000, 3); heads(code, 1, 33, 1)
+    for C in (8, 256, 2048):
+        bn_fin(C, 3017)
+    for M, N in ((37, 64), (1000, 256), (1000, 8), (600000, 8), (4099, 4096)):
+        colsum(M, N, True); colsum(M, N, False)
+    ssim(2, 3, 45, 70); ssim(1, 1, 32, 32)
+    # ---- the training step's shapes (bs 16, 1024^2; tools/hbm_bench.py, colsum_bench.py, ln_bench.py), timed
+    bn(BF16, 256, 16 * 256 * 256, relu=True, dcb=True, timed=True)
+    bn(BF16, 256, 16 * 256 * 256, relu=False, dcb=True, timed=True)
+    ln(BF16, 16 * 4101, 768, dres=True, timed=True)
+    colsum(16 * 256 * 256, 256, True, timed=True); colsum(16 * 256 * 256, 256, False, timed=True)
+    unrope(BF16, 16, 4101, 4096, 12, timed=True)
+    bilinear(BF16, 16, 128, 128, 256, 256, 256, timed=True)
+    bilinear(BF16, 16, 512, 512, 1024, 1024, 32, timed=True)
+    avgpool(BF16, 16, 256 * 256, 256, timed=True)
+    heads(BF16, 16, 1024 * 1024, 3, timed=True)
+    ssim(16, 3, 1024, 1024, timed=True)
+    repack(timed=True)
+
+    # sums that go through fp32 atomics (these outputs outside the BatchNorm entries, whose fp64 replicas are exact
+    # sums of the block partials; one-pass colsum; the loss sums and what is computed from them): their order is not fixed, so
+    # one agreeing pair of runs does not make them repeat (few blocks often agree); they are held to the tolerance
+    # whatever the first two builds show
+    ATOMIC = {"dw", "db", "dlam", "dbias", "dbq", "dbv", "dw2", "db2", "db1"}
+    bad = 0
+    cmp = lambda a, b: "equal" if torch.equal(a, b) else f"{float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300)):.2e}"
+    for name, is_timed, mk in cases:
+        runs = [mk(L) for L in libs]
+        for f, _ in runs:
+            f()
+        torch.cuda.synchronize()
+        line = f"{name}:"
+        for k in runs[0][1]:
+            if k.startswith("_"):
+                continue
+            ref = runs[0][1][k]
+            res = [cmp(r[1][k], ref) for r in runs[1:]]
+            line += f" {k} " + " / ".join(res)
+            if len(res) == 2:                       # parent, parent, new
+                pp, pn = res
+                fixed = pp == "equal" and not (k in ATOMIC and not name.startswith("bn_") or "one-pass" in name or name.startswith("mask_loss"))
+                ok = pn == "equal" if fixed else (pn == "equal" or float(pn) <= max(1e-5, 0.0 if pp == "equal" else float(pp)))
+                if not ok or (pp != "equal" and float(pp) > 1e-5):
+                    line += " <-- " + ("MISS" if not ok else "parent scatter > 1e-5")
+                bad += not ok
+        print(line, flush=True)
+        if is_timed:
+            ts = [[] for _ in libs]
+            for _ in range(rounds):
+                for i, (f, _) in enumerate(runs):
+                    ts[i].append(timed(f, 5))
+            print("    timed: " + " | ".join(f"lib{i} med {sorted(t)[len(t) // 2] * 1e3:8.1f} us min {min(t) * 1e3:8.1f} max {max(t) * 1e3:8.1f}"
+                                             for i, t in enumerate(ts)), flush=True)
+        del runs
+    print(f"glue: {len(cases)} cases, {bad} outputs MISS the rule (equal where the first two builds agree bit for bit, "
+          f"rel-L2 <= max(1e-5, their scatter) elsewhere)")
+    attn(libs, 2, 261, 1)
+    return bad
+
+
 if __name__ == "__main__":
     what, paths = sys.argv[1], sys.argv[2:]
     libs = [Lib(p) for p in paths]
@@ -184,3 +420,5 @@ if __name__ == "__main__":
             attn(libs, 4, 16389, rounds)
     elif what == "lin":
         lin(libs, rounds)
+    elif what == "glue":
+        sys.exit(1 if glue(libs, rounds) else 0)
