@@ -375,3 +375,203 @@ def elastic_field(S, seed, ksize=17, sigma=25.0, alpha=1.0):
         v = sum(w[j] * h[reflect101(np.arange(S) + j - ksize // 2, S)] for j in range(ksize))
         out.append(v * alpha)
     return out
+
+
+# ------------------------------------------------------------------ per-pixel colour members
+def jitter(x, bright, contrast, sat, hue, gray_mean):
+    """ColorJitter in its fixed order (data_ops.hip jitter): brightness, contrast about gray_mean, saturation
+    about the pixel's grey, hue as a rotation about the grey axis by 2*pi*hue; clipped after every stage."""
+    x = np.asarray(x, np.float64)
+    if bright != 1.0:
+        x = np.clip(x * bright, 0, 1)
+    if contrast != 1.0:
+        x = np.clip((x - gray_mean) * contrast + gray_mean, 0, 1)
+    if sat != 1.0:
+        g = 0.299 * x[0] + 0.587 * x[1] + 0.114 * x[2]
+        x = np.clip((x - g) * sat + g, 0, 1)
+    if hue != 0.0:
+        th = 2 * np.pi * hue
+        cs, sn = np.cos(th), np.sin(th)
+        a, b = (1 - cs) / 3, sn / np.sqrt(3.0)
+        r, g, bl = x
+        x = np.clip(np.stack([(cs + a) * r + (a - b) * g + (a + b) * bl,
+                              (a + b) * r + (cs + a) * g + (a - b) * bl,
+                              (a - b) * r + (a + b) * g + (cs + a) * bl]), 0, 1)
+    return x
+
+
+def hsv_shift(x, dh, ds, dv):
+    """HueSaturationValue (data_ops.hip hsv_shift): RGB -> HSV, hue + dh degrees (mod 360), S + ds and
+    V + dv clipped to [0, 1], HSV -> RGB by the six-sector formula."""
+    r, g, b = np.asarray(x, np.float64)
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    d = mx - mn
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h = np.where(mx == r, np.mod((g - b) / d + 6.0, 6.0), np.where(mx == g, (b - r) / d + 2.0, (r - g) / d + 4.0))
+        s = np.where(mx > 0, d / mx, 0.0)
+    h = np.where(d > 0, h, 0.0)
+    h = np.mod(h * 60.0 + dh + 360.0, 360.0) / 60.0
+    s, v = np.clip(s + ds, 0, 1), np.clip(mx + dv, 0, 1)
+    c = v * s
+    xx = c * (1 - np.abs(np.mod(h, 2.0) - 1))
+    m = v - c
+    hi = np.minimum(h.astype(int), 5)
+    z = np.zeros_like(c)
+    rr = np.where((hi == 0) | (hi == 5), c, np.where((hi == 1) | (hi == 4), xx, z))
+    gg = np.where((hi == 1) | (hi == 2), c, np.where((hi == 0) | (hi == 3), xx, z))
+    bb = np.where((hi == 3) | (hi == 4), c, np.where((hi == 2) | (hi == 5), xx, z))
+    return np.stack([rr + m, gg + m, bb + m])
+
+
+def sepia(x):
+    """ToSepia: the fixed 3x3 colour matrix, clipped."""
+    r, g, b = np.asarray(x, np.float64)
+    return np.clip(np.stack([0.393 * r + 0.769 * g + 0.189 * b, 0.349 * r + 0.686 * g + 0.168 * b,
+                             0.272 * r + 0.534 * g + 0.131 * b]), 0, 1)
+
+
+def posterize(x, bits):
+    """Posterize: keep the top `bits` bits of the 8-bit value int(v * 255 + 0.5)."""
+    mask = (0xFF << (8 - bits)) & 0xFF
+    return ((np.asarray(x, np.float64) * 255.0 + 0.5).astype(np.int64) & mask) / 255.0
+
+
+# ------------------------------------------------------------------ the geometry pass (augment_sample_kernel)
+def letterbox_canvas(img_u8, mask_u8, p, S):
+    """LongestMaxSize + centred PadIfNeeded of one sample (data_ops.hip canvas_px and the mask's nearest
+    resize): the [3, S, S] canvas in [0, 1] (cv2 INTER_LINEAR half-pixel mapping, edge replicate, zero pad)
+    and the [S, S] mask canvas (INTER_NEAREST, / 255).  p carries H0, W0, new_h, new_w, pad_h, pad_w."""
+    img = np.asarray(img_u8).astype(np.float64)
+    h0, w0, nh, nw, ph, pw = p.H0, p.W0, p.new_h, p.new_w, p.pad_h, p.pad_w
+    canvas = np.zeros((S, S, 3))
+    mcan = np.zeros((S, S))
+    ys, xs = np.arange(nh), np.arange(nw)
+    v = np.clip((ys + 0.5) * (h0 / nh) - 0.5, 0, h0 - 1)
+    u = np.clip((xs + 0.5) * (w0 / nw) - 0.5, 0, w0 - 1)
+    y0, x0 = v.astype(int), u.astype(int)
+    y1, x1 = np.minimum(y0 + 1, h0 - 1), np.minimum(x0 + 1, w0 - 1)
+    fy, fx = (v - y0)[:, None, None], (u - x0)[None, :, None]
+    top = img[y0][:, x0] * (1 - fx) + img[y0][:, x1] * fx
+    bot = img[y1][:, x0] * (1 - fx) + img[y1][:, x1] * fx
+    canvas[ph:ph + nh, pw:pw + nw] = (top * (1 - fy) + bot * fy) / 255.0
+    if mask_u8 is not None:
+        sy = np.minimum(np.floor(ys * (h0 / nh)).astype(int), h0 - 1)
+        sx = np.minimum(np.floor(xs * (w0 / nw)).astype(int), w0 - 1)
+        mcan[ph:ph + nh, pw:pw + nw] = np.asarray(mask_u8)[sy][:, sx] / 255.0
+    return canvas.transpose(2, 0, 1), mcan
+
+
+def warp_coords(p, S, grid=None, elastic=None):
+    """Canvas index coordinates (cx, cy) that output pixel (x, y) samples, and the `outside` flag, in the
+    kernel's order: output centre (x + .5, y + .5) -> GridDistortion maps (grid: [2][S], x map then y map)
+    -> ElasticTransform displacement (elastic: [2][S][S], dx then dy) -> outside (grid / elastic only)
+    -> radial kdist about the centre -> homography (A [xo, yo, 1]) / (persp [xo, yo] + 1) - 0.5."""
+    yy, xx = np.mgrid[0:S, 0:S].astype(np.float64)
+    xo, yo = xx + 0.5, yy + 0.5
+    outside = np.zeros((S, S), bool)
+    if grid is not None:
+        g = np.asarray(grid, np.float64).reshape(2, S)
+        xo, yo = g[0][None, :] + 0.5 + 0 * yy, g[1][:, None] + 0.5 + 0 * xx
+    if elastic is not None:
+        e = np.asarray(elastic, np.float64).reshape(2, S, S)
+        xo, yo = xo + e[0], yo + e[1]
+    if grid is not None or elastic is not None:
+        outside = (xo < -0.5) | (yo < -0.5) | (xo > S + 0.5) | (yo > S + 0.5)
+    if p.kdist != 0.0:
+        h = 0.5 * S
+        u, v = (xo - h) / h, (yo - h) / h
+        f = 1.0 + p.kdist * (u * u + v * v)
+        xo, yo = h + u * f * h, h + v * f * h
+    A = [float(a) for a in p.A]
+    den = p.persp[0] * xo + p.persp[1] * yo + 1.0
+    cx = (A[0] * xo + A[1] * yo + A[2]) / den - 0.5
+    cy = (A[3] * xo + A[4] * yo + A[5]) / den - 0.5
+    return cx, cy, outside
+
+
+def augment_sample(img_u8, mask_u8, p, S, grid=None, elastic=None):
+    """s3od_augment_sample restated: image = bilinear remap (zero border) of the letterbox canvas at
+    warp_coords, zero where outside; mask = nearest canvas pixel floor(c + 0.5), zero off the canvas / off
+    the resized region / outside.  p.raw == 0 adds the tail jitter -> mult -> hashed Gaussian -> clip.
+    Returns ([3, S, S] in [0, 1] (before Normalize), [S, S])."""
+    canvas, mcan = letterbox_canvas(img_u8, mask_u8, p, S)
+    cx, cy, outside = warp_coords(p, S, grid, elastic)
+    out = np.where(outside[None], 0.0, remap_bilinear(canvas, cx, cy))
+    nx, ny = np.floor(cx + 0.5).astype(np.int64), np.floor(cy + 0.5).astype(np.int64)
+    ok = ~outside & (nx >= 0) & (ny >= 0) & (nx < S) & (ny < S)
+    mask = np.where(ok, mcan[np.clip(ny, 0, S - 1), np.clip(nx, 0, S - 1)], 0.0)
+    if not p.raw:
+        out = jitter(out, p.bright, p.contrast, p.sat, p.hue, p.gray_mean)
+        out = gauss_mult_noise(out, p.gauss_std, [float(m) for m in p.mult], int(p.seed))
+    return out, mask
+
+
+def remap_bound(canvas, cx, cy, S):
+    """Per-pixel bound on |float32 kernel - float64 remap| of the geometry pass, from the reference alone:
+    1e-5 + G * eps.  G: largest difference between canvas values (zero off the canvas) in the 4x4
+    neighbourhood of the sample point, over the channels: a coordinate error of d pixels moves a bilinear
+    sample by at most G * d.  eps = 16 * 2^-24 * max(S, |cx|, |cy|): sixteen float32 roundings on a
+    coordinate of that magnitude (the maps, the affine products, the division by den)."""
+    pad = 3
+    cp = np.pad(canvas, ((0, 0), (pad, pad), (pad, pad)))
+    ix = np.clip(np.floor(cx), -pad, S + 1).astype(np.int64)     # clipped where all 16 neighbours are border
+    iy = np.clip(np.floor(cy), -pad, S + 1).astype(np.int64)
+    lo = np.full(canvas.shape[:1] + cx.shape, np.inf)
+    hi = -lo
+    for dy in range(-1, 3):
+        for dx in range(-1, 3):
+            v = cp[:, np.clip(iy + dy, -pad, S + pad - 1) + pad, np.clip(ix + dx, -pad, S + pad - 1) + pad]
+            lo, hi = np.minimum(lo, v), np.maximum(hi, v)
+    G = (hi - lo).max(0)
+    eps = 16 * 2.0 ** -24 * np.maximum(S, np.maximum(np.abs(cx), np.abs(cy)))
+    return 1e-5 + G * eps
+
+
+def nearest_ambiguous(cx, cy, tol=1e-3):
+    """Pixels whose nearest lookup floor(c + 0.5) sits within tol of a rounding boundary in x or y."""
+    fx, fy = (cx + 0.5) - np.floor(cx + 0.5), (cy + 0.5) - np.floor(cy + 0.5)
+    return (fx < tol) | (fx > 1 - tol) | (fy < tol) | (fy > 1 - tol)
+
+
+# ------------------------------------------------------------------ the photometric chains (s3od_augment_synthetic)
+def colour_noise(x, q):
+    """synth_pixel_kernel: colour group (ColorJitter, then HueSaturationValue when it has a shift), ISONoise with
+    the lightness statistics of the colour group's output, then mult -> hashed Gaussian -> clip."""
+    x = jitter(x, q.bright, q.contrast, q.sat, q.hue, q.gray_mean)
+    if q.hsv_h != 0 or q.hsv_s != 0 or q.hsv_v != 0:
+        x = hsv_shift(x, q.hsv_h, q.hsv_s, q.hsv_v)
+    if q.iso_intensity > 0:
+        x = iso_noise(x, q.iso_intensity, q.iso_color_shift, int(q.seed))
+    return gauss_mult_noise(x, q.gauss_std, [float(m) for m in q.mult], int(q.seed))
+
+
+def filter_pass(x, q, ker=None):
+    """synth_filter_kernel: Downscale + lighting per tap, ZoomBlur, the composed filter (clipped), colour
+    space, Posterize, RandomSnow, in that order."""
+    shadows = [np.array(list(q.shadow[t]), np.float64) for t in range(q.n_shadow)]
+    v = lit(x, down=float(q.down), rbc=(float(q.rbc_alpha), float(q.rbc_beta)), shadows=shadows, shadow_dim=float(q.shadow_dim))
+    if q.zoom_n:
+        v = zoom_blur(v, np.float32([q.zoom[i] for i in range(q.zoom_n)]))
+    v = filter2d(v, ker) if ker is not None and ker.shape[0] > 1 else np.clip(v, 0, 1)
+    if q.color_op == 1:
+        v = sepia(v)
+    elif q.color_op == 2:
+        g = 0.299 * v[0] + 0.587 * v[1] + 0.114 * v[2]
+        v = np.stack([g, g, g])
+    elif q.color_op == 3:
+        v = v[[q.perm[0], q.perm[1], q.perm[2]]]
+    if q.post_bits < 8:
+        v = posterize(v, q.post_bits)
+    if q.snow_point > 0:
+        v = snow_bleach(v, float(q.snow_point), float(q.snow_coeff))
+    return v
+
+
+def synthetic_chain(x, q, ker=None):
+    """s3od_augment_synthetic without CLAHE / ImageCompression / RandomRain (they keep their own functions):
+    order 0: colour + noise per pixel, then the filter pass; order 1 (regular chain): the filter alone,
+    then colour + noise."""
+    if q.order == 1:
+        v = filter2d(x, ker) if ker is not None and ker.shape[0] > 1 else x
+        return colour_noise(v, q)
+    return filter_pass(colour_noise(x, q), q, ker)

@@ -1,7 +1,9 @@
 """MaskDataset file discovery and train/val split (synth_sod/.../dataset.py:34-106) on CPU."""
+import math
 import random
 
 import numpy as np
+import pytest
 from PIL import Image
 
 from s3od_amd.data import MaskDataset, letterbox
@@ -170,3 +172,156 @@ def test_jpeg_restatement_matches_libjpeg():
             assert np.abs(o - lj).mean() * 255 <= 1.0, (S, q, np.abs(o - lj).mean() * 255)
             lo, ll = np.abs(o - u8.transpose(2, 0, 1) / 255.0).mean(), np.abs(lj - u8.transpose(2, 0, 1) / 255.0).mean()
             assert abs(lo - ll) <= 0.05 * ll, (S, q, lo, ll)
+
+
+# ------------------------------------------------------------------ host composition of the warp (GpuAugment._geometry / _draw)
+class _Script:
+    """random.Random stand-in: every draw returns the next scripted value, whatever its distribution, so a
+    test walks one branch of the host code at a time."""
+
+    def __init__(self, values):
+        self.values = list(values)
+
+    def _next(self, lo=None, hi=None):
+        v = self.values.pop(0)
+        assert lo is None or lo <= v <= hi, (v, lo, hi)
+        return v
+
+    def random(self):
+        return self._next(0.0, 1.0)
+
+    def uniform(self, a, b):
+        return self._next(min(a, b), max(a, b))
+
+    def randint(self, a, b):
+        return int(self._next(a, b))
+
+    def gauss(self, mu, sigma):
+        return mu + sigma * self._next()
+
+    def getrandbits(self, n):
+        return int(self._next()) & ((1 << n) - 1)
+
+
+_NO = 0.95                       # a gate draw that takes no branch
+_S = 96
+
+
+def _geo(script):
+    from s3od_amd.data import GpuAugment
+    aug = GpuAugment(_S, mode="regular", device="cpu", seed=0)
+    aug.rng = _Script(script)
+    M = aug._geometry(np.eye(3))
+    assert not aug.rng.values
+    return M
+
+
+def _draw_A(script, mode="regular"):
+    from s3od_amd.data import GpuAugment
+    aug = GpuAugment(_S, mode=mode, device="cpu", seed=0)
+    aug.rng = _Script(script)
+    p, extra = aug._draw(72, 96)
+    assert not aug.rng.values
+    return p
+
+
+def _apply(M, pts):
+    q = (M @ np.concatenate([np.asarray(pts, np.float64), np.ones((len(pts), 1))], 1).T).T
+    return q[:, :2] / q[:, 2:]
+
+
+_PTS = [(0.0, 0.0), (10.0, 3.5), (95.5, 40.25), (96.0, 96.0)]
+_CORNERS = [(0.0, 0.0), (_S, 0.0), (_S, _S), (0.0, _S)]
+_GEO_SCRIPTS = {
+    "hflip": [0.0, _NO, _NO, _NO, _NO],
+    "vflip": [_NO, 0.0, _NO, _NO, _NO],
+    "rot90_1": [_NO, _NO, 0.0, 1, _NO, _NO],
+    "crop": [_NO, _NO, _NO, 0.0, 0.9, 0.05, 2, 5, _NO],
+    "rotate": [_NO, _NO, _NO, _NO, 0.0, 10.0],
+    "all": [0.0, 0.0, 0.0, 3, 0.0, 0.9, 0.05, 2, 5, 0.0, -7.5],
+}
+
+
+def test_geometry_flips_map_points():
+    x, y = np.array(_PTS).T
+    assert np.array_equal(_apply(_geo(_GEO_SCRIPTS["hflip"]), _PTS), np.stack([_S - x, y], 1))
+    assert np.array_equal(_apply(_geo(_GEO_SCRIPTS["vflip"]), _PTS), np.stack([x, _S - y], 1))
+    assert np.array_equal(_geo([_NO] * 5), np.eye(3))
+
+
+def test_geometry_rot90_lands_corners_on_corners():
+    perms = []
+    for k in range(4):
+        got = _apply(_geo([_NO, _NO, 0.0, k, _NO, _NO]), _CORNERS)
+        idx = [_CORNERS.index((float(a), float(b))) for a, b in got]        # exact, or .index raises
+        assert sorted(idx) == [0, 1, 2, 3]
+        assert idx == [(i + idx[0]) % 4 for i in range(4)]                  # a rotation: cyclic order kept
+        perms.append(idx[0])
+    assert perms[0] == 0 and sorted(perms) == [0, 1, 2, 3]                  # k = 0 is the identity, every k differs
+    assert (perms[1] + perms[3]) % 4 == 0 and perms[2] == 2                 # k and 4 - k undo each other
+
+
+def test_geometry_resized_crop_maps_the_crop_to_the_output():
+    M = _geo(_GEO_SCRIPTS["crop"])
+    area, ar = _S * _S * 0.9, math.exp(0.05)
+    cw, ch = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+    assert (cw, ch) == (93, 89)
+    got = _apply(M, [(2.0, 5.0), (2.0 + cw, 5.0 + ch)])
+    assert np.abs(got - [[0, 0], [_S, _S]]).max() < 1e-12
+
+
+def test_geometry_rotate_convention():
+    """Rotate(limit 15) = cv2.getRotationMatrix2D(centre, angle, 1): [[cos, sin], [-sin, cos]] about the centre,
+    so a positive angle moves the point right of the centre upwards (y down: counter-clockwise on screen)."""
+    M = _geo(_GEO_SCRIPTS["rotate"])
+    c, th = _S / 2, math.radians(10.0)
+    assert np.abs(_apply(M, [(c, c)]) - [[c, c]]).max() < 1e-12
+    L = M[:2, :2]
+    assert np.abs(L @ L.T - np.eye(2)).max() < 1e-12 and abs(np.linalg.det(L) - 1) < 1e-12
+    assert np.abs(_apply(M, [(c + 20, c)]) - [[c + 20 * math.cos(th), c - 20 * math.sin(th)]]).max() < 1e-12
+    assert np.abs(M[2] - [0, 0, 1]).max() == 0
+
+
+@pytest.mark.parametrize("name", sorted(_GEO_SCRIPTS))
+def test_draw_packs_the_inverse_of_the_forward_matrix(name):
+    """AugParams.A is the float32 cast of inv(M) (output pixel centre -> canvas), rows 0 and 1; the affine
+    branches leave persp at 0."""
+    script = _GEO_SCRIPTS[name]
+    M = _geo(script)
+    p = _draw_A(script + [_NO, _NO, 1234])          # no colour member, no noise member, the sample seed
+    Minv = np.linalg.inv(M)
+    A = np.array(list(p.A)).reshape(2, 3)
+    assert np.abs(A - Minv[:2]).max() <= 1e-6 * np.abs(Minv[:2]).max(), (A, Minv)
+    assert np.abs(_apply(np.vstack([A, [0, 0, 1]]) @ M, _PTS) - _PTS).max() < 1e-4      # and it undoes M
+    assert p.persp[0] == 0 and p.persp[1] == 0 and p.kdist == 0 and p.seed == 1234
+    if name != "all":
+        assert np.abs(A - np.eye(3)[:2]).max() > 1e-3
+
+
+def test_homography_maps_its_point_pairs():
+    from s3od_amd.data import _homography
+    src = np.array(_CORNERS)
+    dst = src + np.array([[4.0, -6.5], [-7.25, 3.0], [5.5, 8.0], [-3.0, -9.0]])
+    H = _homography(dst, src)
+    assert np.abs(_apply(H, dst) - src).max() < 1e-9
+    assert np.abs(_apply(_homography(src, dst), src) - dst).max() < 1e-9
+    assert abs(H[2, 2] - 1) < 1e-12 and np.abs(H[2, :2]).max() > 1e-5          # genuinely projective
+
+
+def test_perspective_composes_homography_then_inverse_geometry():
+    """Perspective draw: output pixel -> H (jittered corners -> the square's corners) -> inv(M) -> canvas.
+    With a non-trivial M (flip, crop, rotation) the swapped product inv(M)-then-H lands pixels away."""
+    from s3od_amd.data import _homography
+    geo = _GEO_SCRIPTS["all"]
+    jit = [0.4, -0.65, -0.7, 0.3, 0.55, 0.8, -0.3, -0.9]                        # standard-normal draws, scale 0.07 * S
+    p = _draw_A(geo + [0.0, 0.99, 0.07] + jit, mode="synthetic")                # distortion OneOf: member 3, Perspective
+    M = _geo(geo)
+    src = np.array(_CORNERS)
+    dst = src + 0.07 * _S * np.array(jit).reshape(4, 2)
+    Tot = np.array([list(p.A)[:3], list(p.A)[3:], [p.persp[0], p.persp[1], 1.0]])
+    Mi = np.linalg.inv(M)
+    assert p.raw == 1 and p.kdist == 0 and abs(p.persp[0]) > 1e-5
+    assert np.abs(_apply(Tot, dst) - _apply(Mi, src)).max() < 5e-4              # float32 parameters on ~1e2 coordinates
+    H = _homography(dst, src)
+    assert np.abs(_apply(Tot, src) - _apply(Mi, _apply(H, src))).max() < 5e-4
+    assert np.abs(_apply(Tot, src) - _apply(H, _apply(Mi, src))).max() > 1.0    # the swapped order is pixels away
