@@ -158,7 +158,9 @@ def test_mask_heads_bwd(dtype, NM, B, HW):
 
 # ------------------------------------------------------------------------------------------------ bilinear forward
 UP2 = [(ih, iw, 2 * ih, 2 * iw) for ih, iw in [(1, 1), (1, 5), (5, 1), (7, 9), (16, 16)]]
-GENERIC = [(12, 10, 25, 17), (7, 9, 15, 18), (5, 5, 5, 5), (3, 4, 12, 4)]
+GENERIC = [(12, 10, 25, 17), (7, 9, 15, 18), (5, 5, 5, 5), (3, 4, 12, 4),
+           (1, 1, 7, 5), (1, 6, 9, 6), (2, 3, 37, 41), (3, 3, 100, 7),          # a 1-pixel axis, large ratios
+           (25, 17, 12, 10), (9, 8, 3, 3), (8, 8, 4, 4), (7, 5, 1, 1)]          # down-scales
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
