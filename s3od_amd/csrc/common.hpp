@@ -84,15 +84,28 @@ template <> DEV void store8<bf16>(bf16* p, const float* v) {
   *(bf16x8*)p = a;
 }
 
-DEV float warp_sum(float v) {
+// butterfly reductions over the 64 lanes of a wave: every lane gets the result
+template <typename T> DEV T warp_sum(T v) {      // float, double
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
-DEV float warp_max(float v) {
+DEV int wave_min_i(int v) {
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
   return v;
+}
+DEV int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+
+// torchvision / albumentations Normalize with the ImageNet statistics, v in [0, 1]: float32 value - float64 mean,
+// / float64 std, rounded once to float32 (numpy's arithmetic on a float32 image)
+DEV float imagenet_norm(float v, int c) {
+  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
+  return (float)(((double)v - mean[c]) / stdv[c]);
 }
 
 DEV float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }

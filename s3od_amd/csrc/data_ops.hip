@@ -68,7 +68,7 @@ struct SynthParams {
 
 // workspace layout (floats): scratch image [3][S][S] | JPEG Y [Sp][Sp] | JPEG Cb, Cr [Sp/2][Sp/2] each |
 // CLAHE histograms int [64][256] | CLAHE LUTs [64][256] | 8 doubles of statistics;  Sp = 16 * ceil(S / 16)
-static inline long ws_sp(int S) { return 16L * ((S + 15) / 16); }
+static __host__ __device__ inline long ws_sp(int S) { return 16L * ((S + 15) / 16); }
 static inline long ws_jpeg_y(int S) { return 3L * S * S; }
 static inline long ws_jpeg_c(int S) { return ws_jpeg_y(S) + ws_sp(S) * ws_sp(S); }
 static inline long ws_hist(int S) { return ws_jpeg_c(S) + 2 * (ws_sp(S) / 2) * (ws_sp(S) / 2); }
@@ -220,23 +220,44 @@ DEV bool in_poly5(const float* v, float px, float py) {
   }
   return in;
 }
-DEV void normalize_store(float* out, long plane, long o, const float* rgb) {
-  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-#pragma unroll
-  for (int c = 0; c < 3; c++) out[c * plane + o] = (float)(((double)rgb[c] - mean[c]) / stdv[c]);
+// the per-pixel kernels' thread: pixel (x, y) of an [n][S][S] picture on a (cdiv(S, 256), S[, n]) grid of 256-thread blocks.  A kernel names
+// plane() and o() once, after its bounds return, for load_rgb / store_rgb: recomputed inside them they changed its register allocation
+struct Pix {
+  int x, y, S;
+  DEV bool in() const { return x < S; }
+  DEV long plane() const { return (long)S * S; }
+  DEV long o() const { return (long)y * S + x; }          // offset of the pixel inside a plane
+};
+DEV Pix this_pixel(int S) { return {(int)(blockIdx.x * blockDim.x + threadIdx.x), (int)blockIdx.y, S}; }
+DEV void load_rgb(const float* x, long plane, long o, float* rgb) { rgb[0] = x[o]; rgb[1] = x[plane + o]; rgb[2] = x[2 * plane + o]; }
+// normalize: ImageNet-normalised, else raw [0, 1].  Call it with a constant flag, under the caller's own branch: given the
+// chain kernels' runtime flag it shares the stores of the two paths, and the sepia / grey sums before them contract differently
+DEV void store_rgb(float* out, long plane, long o, const float* rgb, int normalize) {
+  if (normalize) for (int c = 0; c < 3; c++) out[c * plane + o] = imagenet_norm(rgb[c], c);
+  else for (int c = 0; c < 3; c++) out[c * plane + o] = rgb[c];
+}
+// end of the noise group, channel c of pixel pix: MultiplicativeNoise, hashed GaussNoise, clip
+DEV float noise_tail(float v, float mult, float gauss_std, unsigned seed, unsigned pix, int c) {
+  v *= mult;
+  if (gauss_std > 0.f) v += gauss_std * gauss(seed, pix, c);
+  return clamp01(v);
+}
+// 8-bit RGB (as floats) of pixel o of a [0, 1] picture
+DEV void rgb8(const float* x, long plane, long o, float* v) {
+  v[0] = rintf(clamp01(x[o]) * 255.f); v[1] = rintf(clamp01(x[plane + o]) * 255.f); v[2] = rintf(clamp01(x[2 * plane + o]) * 255.f);
 }
 DEV long floor_div(long a, long b) { long q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
 }  // namespace
 
 __global__ void augment_sample_kernel(const unsigned char* __restrict__ img, const unsigned char* __restrict__ mask,
                                       AugParams P, int S, float* __restrict__ out_img, float* __restrict__ out_mask) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= S) return;
-  const long plane = (long)S * S, o = (long)y * S + x;
-  float xo = x + 0.5f, yo = y + 0.5f;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
+  float xo = p.x + 0.5f, yo = p.y + 0.5f;
   // distortion group (transforms.py:161-181): remap of the geometric result, BORDER_CONSTANT 0
   bool outside = false;
-  if (P.grid) { xo = P.grid[x] + 0.5f; yo = P.grid[S + y] + 0.5f; }
+  if (P.grid) { xo = P.grid[p.x] + 0.5f; yo = P.grid[S + p.y] + 0.5f; }
   if (P.elastic) { xo += P.elastic[o]; yo += P.elastic[plane + o]; }
   if (P.grid || P.elastic) outside = xo < -0.5f || yo < -0.5f || xo > S + 0.5f || yo > S + 0.5f;
   if (P.kdist != 0.f) {       // radial distortion about the image centre (normalised radius)
@@ -263,18 +284,13 @@ __global__ void augment_sample_kernel(const unsigned char* __restrict__ img, con
     rgb[c] = outside ? 0.f : acc;
   }
   if (P.raw) {
-#pragma unroll
-    for (int c = 0; c < 3; c++) out_img[c * plane + o] = rgb[c];
+    store_rgb(out_img, plane, o, rgb, 0);
   } else {
     // ColorJitter (fixed order brightness, contrast, saturation, hue), clipped like uint8 images
     jitter(rgb, P.bright, P.contrast, P.sat, P.hue, P.gray_mean);
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-      float v = rgb[c] * P.mult[c];
-      if (P.gauss_std > 0.f) v += P.gauss_std * gauss(P.seed, (unsigned)o, c);
-      rgb[c] = clamp01(v);
-    }
-    normalize_store(out_img, plane, o, rgb);
+    for (int c = 0; c < 3; c++) rgb[c] = noise_tail(rgb[c], P.mult[c], P.gauss_std, P.seed, (unsigned)o, c);
+    store_rgb(out_img, plane, o, rgb, 1);
   }
   if (out_mask) {   // nearest (cv2 INTER_NEAREST on the resize, nearest on the geometric warp)
     int nx = (int)floorf(cx + 0.5f), ny = (int)floorf(cy + 0.5f);
@@ -300,21 +316,21 @@ struct ElasticParams {
 };
 
 __global__ void elastic_h_kernel(ElasticParams P, int S, float* __restrict__ tmp) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, c = blockIdx.z;
-  if (x >= S) return;
-  const int r = P.ksize / 2;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const int r = P.ksize / 2, c = blockIdx.z;
   float acc = 0.f;
-  for (int j = -r; j <= r; j++) acc += P.w[j + r] * gauss(P.seed, (unsigned)((long)y * S + reflect101(x + j, S)), 8 + c);
-  tmp[((long)c * S + y) * S + x] = acc;
+  for (int j = -r; j <= r; j++) acc += P.w[j + r] * gauss(P.seed, (unsigned)((long)p.y * S + reflect101(p.x + j, S)), 8 + c);
+  tmp[((long)c * S + p.y) * S + p.x] = acc;
 }
 
 __global__ void elastic_v_kernel(ElasticParams P, int S, const float* __restrict__ tmp, float* __restrict__ out) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y, c = blockIdx.z;
-  if (x >= S) return;
-  const int r = P.ksize / 2;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const int r = P.ksize / 2, c = blockIdx.z;
   float acc = 0.f;
-  for (int j = -r; j <= r; j++) acc += P.w[j + r] * tmp[((long)c * S + reflect101(y + j, S)) * S + x];
-  out[((long)c * S + y) * S + x] = acc * P.alpha;
+  for (int j = -r; j <= r; j++) acc += P.w[j + r] * tmp[((long)c * S + reflect101(p.y + j, S)) * S + p.x];
+  out[((long)c * S + p.y) * S + p.x] = acc * P.alpha;
 }
 
 // ---------------------------------------------------------------- CLAHE (cv2.createCLAHE on L of Lab, 8x8 tiles)
@@ -326,8 +342,8 @@ __global__ void clahe_hist_kernel(const float* __restrict__ x, int S, int* __res
   const long plane = (long)S * S;
   for (int i = threadIdx.x; i < T * T; i += blockDim.x) {
     const int px = tx * T + i % T, py = ty * T + i / T;
-    const long o = (long)py * S + px;
-    float rgb[3] = {x[o], x[plane + o], x[2 * plane + o]}, L, A, B;
+    float rgb[3], L, A, B;
+    load_rgb(x, plane, (long)py * S + px, rgb);
     rgb2lab(rgb, L, A, B);
     atomicAdd(&h[lab_l8(L)], 1);
   }
@@ -360,17 +376,18 @@ __global__ void clahe_lut_kernel(int* __restrict__ hist, float clip, int S, floa
 }
 
 __global__ void clahe_apply_kernel(float* __restrict__ x, int S, const float* __restrict__ lut) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
-  if (px >= S) return;
-  const long plane = (long)S * S, o = (long)py * S + px;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
   const int T = S / 8;
   const float inv = 1.f / T;
-  float txf = px * inv - 0.5f, tyf = py * inv - 0.5f;
+  float txf = p.x * inv - 0.5f, tyf = p.y * inv - 0.5f;
   int tx1 = (int)floorf(txf), ty1 = (int)floorf(tyf);
   const float xa = txf - tx1, ya = tyf - ty1;
   int tx2 = min(tx1 + 1, 7), ty2 = min(ty1 + 1, 7);
   tx1 = max(tx1, 0); ty1 = max(ty1, 0);
-  float rgb[3] = {x[o], x[plane + o], x[2 * plane + o]}, L, A, B;
+  float rgb[3], L, A, B;
+  load_rgb(x, plane, o, rgb);
   rgb2lab(rgb, L, A, B);
   const int v = lab_l8(L);
   const float* l1 = lut + (ty1 * 8) * 256;
@@ -379,25 +396,23 @@ __global__ void clahe_apply_kernel(float* __restrict__ x, int S, const float* __
               (l2[tx1 * 256 + v] * (1.f - xa) + l2[tx2 * 256 + v] * xa) * ya;
   const float l8 = fminf(fmaxf(rintf(res), 0.f), 255.f);
   lab2rgb(l8 * (100.f / 255.f), A, B, rgb);
-#pragma unroll
-  for (int c = 0; c < 3; c++) x[c * plane + o] = rgb[c];
+  store_rgb(x, plane, o, rgb, 0);
 }
 
 // ---------------------------------------------------------------- per-pixel groups
 // sum and sum of squares (fp64) of the HLS lightness after the colour group: ISONoise's
 // cv2.meanStdDev(hls)[1] (population standard deviation)
 __global__ void lightness_stats_kernel(const float* __restrict__ x, SynthParams P, int S, double* __restrict__ st) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
+  const Pix p = this_pixel(S);
   double a = 0.0, b = 0.0;
-  if (px < S) {
-    const long plane = (long)S * S, o = (long)py * S + px;
-    float rgb[3] = {x[o], x[plane + o], x[2 * plane + o]}, h, l, s;
+  if (p.in()) {
+    float rgb[3], h, l, s;
+    load_rgb(x, p.plane(), p.o(), rgb);
     colour_group(rgb, P);
     rgb2hls(rgb, h, l, s);
     a = l; b = (double)l * l;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+  a = warp_sum(a); b = warp_sum(b);
   __shared__ double red[2][4];
   const int w = threadIdx.x / 64;
   if ((threadIdx.x & 63) == 0) { red[0][w] = a; red[1][w] = b; }
@@ -414,10 +429,11 @@ __global__ void lightness_stats_kernel(const float* __restrict__ x, SynthParams 
 // MultiplicativeNoise), per pixel.  in -> out (may alias); normalize: write ImageNet-normalised.
 __global__ void synth_pixel_kernel(const float* in, float* out, SynthParams P, int S, const double* __restrict__ st,
                                    int normalize) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
-  if (px >= S) return;
-  const long plane = (long)S * S, o = (long)py * S + px;
-  float rgb[3] = {in[o], in[plane + o], in[2 * plane + o]};
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
+  float rgb[3];
+  load_rgb(in, plane, o, rgb);
   colour_group(rgb, P);
   if (P.iso_intensity > 0.f) {
     // iso_noise: hue += N(0, color_shift * 360 * intensity); L += Poisson(std_L * intensity * 255) / 255 * (1 - L)
@@ -433,17 +449,9 @@ __global__ void synth_pixel_kernel(const float* in, float* out, SynthParams P, i
     hls2rgb(h, l, s, rgb);
   }
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    float v = rgb[c] * P.mult[c];
-    if (P.gauss_std > 0.f) v += P.gauss_std * gauss(P.seed, (unsigned)o, c);
-    rgb[c] = clamp01(v);
-  }
-  if (normalize) {
-    normalize_store(out, plane, o, rgb);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; c++) out[c * plane + o] = rgb[c];
-  }
+  for (int c = 0; c < 3; c++) rgb[c] = noise_tail(rgb[c], P.mult[c], P.gauss_std, P.seed, (unsigned)o, c);
+  if (normalize) store_rgb(out, plane, o, rgb, 1);
+  else store_rgb(out, plane, o, rgb, 0);
 }
 
 // ---------------------------------------------------------------- ImageCompression (JPEG, 4:2:0)
@@ -464,7 +472,7 @@ __global__ void jpeg_block_kernel(const float* __restrict__ x, int S, int qualit
                                   float* __restrict__ cplane) {
   __shared__ float f[8][8], t[8][8], dm[8][8];
   const int tid = threadIdx.x, i = tid & 7, j = tid >> 3;
-  const int Sp = 16 * ((S + 15) / 16), nby = Sp / 8, nbc = Sp / 16;
+  const int Sp = (int)ws_sp(S), nby = Sp / 8, nbc = Sp / 16;
   const long plane = (long)S * S;
   int b = blockIdx.x, comp, bx, by;
   if (b < nby * nby) { comp = 0; bx = b % nby; by = b / nby; }
@@ -476,17 +484,18 @@ __global__ void jpeg_block_kernel(const float* __restrict__ x, int S, int qualit
   float sample;
   if (comp == 0) {
     const int px = min(bx * 8 + i, S - 1), py = min(by * 8 + j, S - 1);
-    const long o = (long)py * S + px;
-    float r = rintf(clamp01(x[o]) * 255.f), g = rintf(clamp01(x[plane + o]) * 255.f), bl = rintf(clamp01(x[2 * plane + o]) * 255.f);
-    sample = rintf(0.299f * r + 0.587f * g + 0.114f * bl);
+    float v[3];
+    rgb8(x, plane, (long)py * S + px, v);
+    sample = rintf(0.299f * v[0] + 0.587f * v[1] + 0.114f * v[2]);
   } else {
     int sum = 0;
     for (int dy = 0; dy < 2; dy++)
       for (int dx = 0; dx < 2; dx++) {
         const int px = min(2 * (bx * 8 + i) + dx, S - 1), py = min(2 * (by * 8 + j) + dy, S - 1);
-        const long o = (long)py * S + px;
-        float r = rintf(clamp01(x[o]) * 255.f), g = rintf(clamp01(x[plane + o]) * 255.f), bl = rintf(clamp01(x[2 * plane + o]) * 255.f);
-        float c = comp == 1 ? -0.168736f * r - 0.331264f * g + 0.5f * bl + 128.f : 0.5f * r - 0.418688f * g - 0.081312f * bl + 128.f;
+        float v[3];
+        rgb8(x, plane, (long)py * S + px, v);
+        float c = comp == 1 ? -0.168736f * v[0] - 0.331264f * v[1] + 0.5f * v[2] + 128.f
+                            : 0.5f * v[0] - 0.418688f * v[1] - 0.081312f * v[2] + 128.f;
         sum += (int)fminf(fmaxf(rintf(c), 0.f), 255.f);
       }
     sample = (float)((sum + 2) >> 2);
@@ -521,12 +530,12 @@ __global__ void jpeg_block_kernel(const float* __restrict__ x, int S, int qualit
 // decoder side: h2v2 "fancy" (triangle) chroma upsampling, YCbCr -> RGB, 8-bit rounding, back to [0, 1]
 __global__ void jpeg_rgb_kernel(const float* __restrict__ yplane, const float* __restrict__ cplane, int S,
                                 float* __restrict__ x) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
-  if (px >= S) return;
-  const int Sp = 16 * ((S + 15) / 16), Sc = Sp / 2, Wc = (S + 1) / 2;
-  const long plane = (long)S * S, o = (long)py * S + px;
-  const int nx = px >> 1, ny = py >> 1;
-  const int fx = min(max((px & 1) ? nx + 1 : nx - 1, 0), Wc - 1), fy = min(max((py & 1) ? ny + 1 : ny - 1, 0), Wc - 1);
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
+  const int Sp = (int)ws_sp(S), Sc = Sp / 2, Wc = (S + 1) / 2;
+  const int nx = p.x >> 1, ny = p.y >> 1;
+  const int fx = min(max((p.x & 1) ? nx + 1 : nx - 1, 0), Wc - 1), fy = min(max((p.y & 1) ? ny + 1 : ny - 1, 0), Wc - 1);
   float cc[2];
 #pragma unroll
   for (int k = 0; k < 2; k++) {
@@ -534,10 +543,11 @@ __global__ void jpeg_rgb_kernel(const float* __restrict__ yplane, const float* _
     const int s = 9 * (int)c[ny * Sc + nx] + 3 * (int)c[ny * Sc + fx] + 3 * (int)c[fy * Sc + nx] + (int)c[fy * Sc + fx];
     cc[k] = (float)((s + 8) >> 4) - 128.f;
   }
-  const float Y = yplane[(long)py * Sp + px];
+  const float Y = yplane[(long)p.y * Sp + p.x];
   float rgb[3] = {Y + 1.402f * cc[1], Y - 0.344136f * cc[0] - 0.714136f * cc[1], Y + 1.772f * cc[0]};
 #pragma unroll
-  for (int c = 0; c < 3; c++) x[c * plane + o] = fminf(fmaxf(rintf(rgb[c]), 0.f), 255.f) * (1.f / 255.f);
+  for (int c = 0; c < 3; c++) rgb[c] = fminf(fmaxf(rintf(rgb[c]), 0.f), 255.f) * (1.f / 255.f);
+  store_rgb(x, plane, o, rgb, 0);
 }
 
 // ---------------------------------------------------------------- filter pass
@@ -584,16 +594,16 @@ DEV float blur_in(const float* __restrict__ x, const SynthParams& P, int S, int 
 // compose into one kernel; BORDER_REFLECT_101).  normalize = 0 writes raw [0, 1] RGB (rain / regular chain).
 __global__ void synth_filter_kernel(const float* __restrict__ x, const float* __restrict__ kw, SynthParams P, int S,
                                     float* __restrict__ out, int normalize) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
-  if (px >= S) return;
-  const long plane = (long)S * S, o = (long)py * S + px;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
   const int r = P.ksize / 2;
   const int Sd = max(1, (int)(S * P.down));
   float rgb[3] = {0.f, 0.f, 0.f};
   for (int dy = -r; dy <= r; dy++) {
-    const int yy = reflect101(py + dy, S);
+    const int yy = reflect101(p.y + dy, S);
     for (int dx = -r; dx <= r; dx++) {
-      const int xx = reflect101(px + dx, S);
+      const int xx = reflect101(p.x + dx, S);
       const float w = kw ? kw[(dy + r) * P.ksize + (dx + r)] : 1.f;
 #pragma unroll
       for (int c = 0; c < 3; c++) rgb[c] += w * blur_in(x, P, S, Sd, xx, yy, c);
@@ -622,12 +632,8 @@ __global__ void synth_filter_kernel(const float* __restrict__ x, const float* __
     const float thr = P.snow_point * 0.5f + 1.f / 3.f;
     if (l < thr) { l = fminf(l * P.snow_coeff, 1.f); hls2rgb(h, l, s, rgb); }
   }
-  if (normalize) {
-    normalize_store(out, plane, o, rgb);
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; c++) out[c * plane + o] = rgb[c];
-  }
+  if (normalize) store_rgb(out, plane, o, rgb, 1);
+  else store_rgb(out, plane, o, rgb, 0);
 }
 
 // ---------------------------------------------------------------- RandomRain ("default")
@@ -649,15 +655,15 @@ __global__ void rain_lines_kernel(float* __restrict__ x, SynthParams P, int S) {
 
 // cv2.blur(rain_blur x rain_blur, BORDER_REFLECT_101), HSV V * brightness_coefficient (= RGB * coeff), Normalize
 __global__ void rain_final_kernel(const float* __restrict__ x, SynthParams P, int S, float* __restrict__ out) {
-  const int px = blockIdx.x * blockDim.x + threadIdx.x, py = blockIdx.y;
-  if (px >= S) return;
-  const long plane = (long)S * S, o = (long)py * S + px;
+  const Pix p = this_pixel(S);
+  if (!p.in()) return;
+  const long plane = p.plane(), o = p.o();
   const int r = P.rain_blur / 2;
   float rgb[3] = {0.f, 0.f, 0.f};
   for (int dy = -r; dy <= r; dy++) {
-    const long row = (long)reflect101(py + dy, S) * S;
+    const long row = (long)reflect101(p.y + dy, S) * S;
     for (int dx = -r; dx <= r; dx++) {
-      const long q = row + reflect101(px + dx, S);
+      const long q = row + reflect101(p.x + dx, S);
 #pragma unroll
       for (int c = 0; c < 3; c++) rgb[c] += x[c * plane + q];
     }
@@ -665,7 +671,13 @@ __global__ void rain_final_kernel(const float* __restrict__ x, SynthParams P, in
   const float k = P.rain_bright / (float)(P.rain_blur * P.rain_blur);
 #pragma unroll
   for (int c = 0; c < 3; c++) rgb[c] = clamp01(rgb[c] * k);
-  normalize_store(out, plane, o, rgb);
+  store_rgb(out, plane, o, rgb, 1);
+}
+
+// ISONoise's statistics of picture x after the colour group: st[0..1] zeroed, then summed
+static void launch_lightness_stats(const float* x, const SynthParams& P, int S, double* st, hipStream_t stream) {
+  (void)hipMemsetAsync(st, 0, 2 * sizeof(double), stream);
+  hipLaunchKernelGGL(lightness_stats_kernel, dim3(cdiv(S, 256), S), dim3(256), 0, stream, x, P, S, st);
 }
 
 extern "C" {
@@ -703,10 +715,7 @@ int s3od_augment_synthetic(float* raw, const void* params, const float* kw, int 
       hipLaunchKernelGGL(synth_filter_kernel, grid, blk, 0, st, raw, kwp, F, S, scratch, 0);
       src = scratch;
     }
-    if (P.iso_intensity > 0.f) {
-      (void)hipMemsetAsync(stats, 0, 2 * sizeof(double), st);
-      hipLaunchKernelGGL(lightness_stats_kernel, grid, blk, 0, st, src, P, S, stats);
-    }
+    if (P.iso_intensity > 0.f) launch_lightness_stats(src, P, S, stats, st);
     hipLaunchKernelGGL(synth_pixel_kernel, grid, blk, 0, st, src, out, P, S, (const double*)stats, 1);
     return s3od_check_launch("augment_synthetic (regular chain)");
   }
@@ -717,10 +726,7 @@ int s3od_augment_synthetic(float* raw, const void* params, const float* kw, int 
     hipLaunchKernelGGL(clahe_lut_kernel, dim3(64), dim3(64), 0, st, hist, P.clahe_clip, S, lut);
     hipLaunchKernelGGL(clahe_apply_kernel, grid, blk, 0, st, raw, S, lut);
   }
-  if (P.iso_intensity > 0.f) {
-    (void)hipMemsetAsync(stats, 0, 2 * sizeof(double), st);
-    hipLaunchKernelGGL(lightness_stats_kernel, grid, blk, 0, st, raw, P, S, stats);
-  }
+  if (P.iso_intensity > 0.f) launch_lightness_stats(raw, P, S, stats, st);
   hipLaunchKernelGGL(synth_pixel_kernel, grid, blk, 0, st, raw, raw, P, S, (const double*)stats, 0);
   if (P.jpeg_quality > 0) {
     // image_compression: cv2.imencode(".jpg", quality) + imdecode (standard tables, 4:2:0)

@@ -44,11 +44,8 @@ DEV void pre_pixel(const unsigned char* __restrict__ img, int H0, int W0, int ne
   }
 }
 
-DEV float pre_norm(int v, int c) {
-  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-  float t = (float)v / 255.0f;                      // float32 / python float -> float32 (numpy 2)
-  return (float)(((double)t - mean[c]) / stdv[c]);  // - float64 mean, / float64 std
-}
+// 8-bit value -> normalised: float32 / python float -> float32 (numpy 2), then imagenet_norm's float64 steps
+DEV float pre_norm(int v, int c) { return imagenet_norm((float)v / 255.0f, c); }
 
 // one thread per destination pixel of the resized (new_h x new_w) image; writes normalised fp32
 // into the S x S canvas at (pad_h + y, pad_w + x).  The canvas must be pre-filled with the
@@ -66,8 +63,7 @@ __global__ void canvas_fill_kernel(float* out, int S) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 3L * S * S) return;
   int c = i / ((long)S * S);
-  const double mean[3] = {0.485, 0.456, 0.406}, stdv[3] = {0.229, 0.224, 0.225};
-  out[i] = (float)((0.0 - mean[c]) / stdv[c]);
+  out[i] = imagenet_norm(0.f, c);
 }
 
 // ---------------------------------------------------------------- batched entries: descriptor tables
@@ -179,17 +175,6 @@ constexpr int ST_WORDS = 72, ST_MAXBLK = 1024;
 DEV void stats_init(unsigned* __restrict__ st) {
   const int t = threadIdx.x;
   if (t < ST_WORDS) st[t] = (t == ST_X0 || t == ST_Y0) ? 0x7fffffffu : 0u;
-}
-
-DEV int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-DEV int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
 }
 
 // Block `blk` of `nblk` (256 threads) counts its share of the N = H0 W0 pixels of planes [NM][N]: one wave-wide ballot

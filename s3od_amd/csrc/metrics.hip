@@ -44,12 +44,6 @@ struct Tables {
   double k7[49];     // matlab_style_gauss2D((7,7), 5)
 };
 
-DEV double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 // block-wide sum of NV doubles, thread 0 adds them to dst[slot[i]]
 template <int NV>
 DEV void block_add(double (&v)[NV], double* acc, const int (&slot)[NV]) {
@@ -57,7 +51,7 @@ DEV void block_add(double (&v)[NV], double* acc, const int (&slot)[NV]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < NV; i++) {
-    double s = wave_sum(v[i]);
+    double s = warp_sum(v[i]);
     if (lane == 0) red[w][i] = s;
   }
   __syncthreads();

@@ -6,7 +6,9 @@
 ``int(n * val_split)`` files are the validation split, optional ``debug_subset_fraction``.
 Workers only decode (PIL -> uint8); ``GpuAugment`` turns a list of decoded samples into the
 reference's batch dict ``{"images": fp32 [B,3,S,S] (ImageNet-normalised), "masks": fp32 [B,S,S]}``
-on the GPU with one fused HIP launch per sample (``s3od_augment_sample``, data_ops.hip):
+on the GPU.  Per sample, ``GpuAugment.draw`` draws everything random on the host into one ``SampleDraw``
+(no device is touched) and ``GpuAugment.launch`` uploads its tables and runs one fused HIP launch
+(``s3od_augment_sample``, data_ops.hip) plus, for a draw with a chain, ``s3od_augment_synthetic``:
 
 * mode "test": LongestMaxSize(S) + centred PadIfNeeded(S, fill 0) + Normalize (transforms.py:14-28);
 * mode "regular": + HorizontalFlip 0.5, VerticalFlip 0.2, RandomRotate90 0.2, RandomResizedCrop
@@ -32,7 +34,8 @@ on the GPU with one fused HIP launch per sample (``s3od_augment_sample``, data_o
 albumentations / cv2 are not in this image, so the augmentations follow the published semantics
 of albumentations 2.0.8 but are NOT bit-matched to it ("parity unpinned"); every member is checked
 against the numpy restatement in oracle/augment_oracle.py (tests/test_gpu_augment.py, JPEG pinned
-to libjpeg through PIL) and the "test" mode against tests/test_gpu_data.py.
+to libjpeg through PIL) and the "test" mode against tests/test_gpu_data.py.  The random stream of
+``draw`` is pinned byte for byte by tests/golden/augment_draws.npz (tests/test_data_cpu.py).
 """
 from __future__ import annotations
 
@@ -40,6 +43,7 @@ import ctypes
 import math
 import os
 import random
+from dataclasses import dataclass
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -105,6 +109,14 @@ class AugParams(ctypes.Structure):
                 ("seed", ctypes.c_uint), ("persp", ctypes.c_float * 2), ("kdist", ctypes.c_float), ("raw", ctypes.c_int),
                 ("grid", ctypes.c_void_p), ("elastic", ctypes.c_void_p)]
 
+    @classmethod
+    def identity(cls, h0: int, w0: int, S: int):
+        """The "test" mode sample: the letterbox of an h0 x w0 source in the S x S canvas, identity warp, no photometrics."""
+        p = cls()
+        p.A[0] = p.A[4] = 1.0
+        GpuAugment._fill(p, h0, w0, *letterbox(h0, w0, S))
+        return p
+
 
 class SynthParams(ctypes.Structure):
     """Mirror of struct SynthParams (csrc/data_ops.hip): the photometric chain after the geometry pass."""
@@ -143,8 +155,9 @@ def augment_ws_floats(S: int) -> int:
     return int(n.value)
 
 
-def gaussian_taps(ksize: int, sigma: float) -> np.ndarray:
-    """cv2.getGaussianKernel(ksize, sigma) (sigma > 0)."""
+def gaussian_taps(ksize: int, sigma: Optional[float] = None) -> np.ndarray:
+    """cv2.getGaussianKernel(ksize, sigma); sigma None or 0: cv2's default for that size."""
+    sigma = sigma or 0.3 * ((ksize - 1) * 0.5 - 1) + 0.8
     x = np.arange(ksize) - (ksize - 1) / 2
     g = np.exp(-x ** 2 / (2 * sigma ** 2))
     return g / g.sum()
@@ -154,8 +167,7 @@ def elastic_params(seed: int, alpha: float = 1.0, sigma: float = 25.0, ksize: in
     """ElasticTransform(alpha=1, sigma=25) displacement parameters (transforms.py:169-173; albumentations
     2.0.8 generate_displacement_fields with approximate=False, i.e. a 17x17 Gaussian)."""
     e = ElasticParams()
-    for i, v in enumerate(gaussian_taps(ksize, sigma)):
-        e.w[i] = float(v)
+    e.w[:ksize] = [float(v) for v in gaussian_taps(ksize, sigma)]
     e.ksize, e.alpha, e.seed = ksize, float(alpha), seed & 0xFFFFFFFF
     return e
 
@@ -199,10 +211,7 @@ def _one_of(r, p, weights):
 
 
 def _gauss_kernel(k, sigma=None):
-    sigma = sigma or 0.3 * ((k - 1) * 0.5 - 1) + 0.8            # cv2.getGaussianKernel default
-    x = np.arange(k) - (k - 1) / 2
-    g = np.exp(-x ** 2 / (2 * sigma ** 2))
-    g /= g.sum()
+    g = gaussian_taps(k, sigma)
     return np.outer(g, g)
 
 
@@ -265,6 +274,22 @@ def _conv_full(a, b):
     return convolve2d(a, b, mode="full")
 
 
+def _gray_mean(img: np.ndarray) -> float:
+    """Mean grey of a uint8 RGB image, in [0, 1] (ColorJitter's contrast pivot before the caller's scaling)."""
+    return (img[..., 0] * 0.299 + img[..., 1] * 0.587 + img[..., 2] * 0.114).mean() / 255.0
+
+
+@dataclass
+class SampleDraw:
+    """One sample's draws, host data only; GpuAugment.launch uploads the tables and fills the records' pointer fields in place."""
+    geometry: AugParams                                         # geometry pass (+ the regular mode's one-pass photometrics)
+    chain: Optional[SynthParams] = None                         # second stage: synthetic chain, or the regular chain (order 1)
+    kernel: Optional[np.ndarray] = None                         # composed filter, float32 [ksize][ksize] (chain.ksize > 1)
+    drops: Optional[np.ndarray] = None                          # RandomRain drop starts, int32 [rain_n][2]
+    grid: Optional[np.ndarray] = None                           # GridDistortion source maps, float32 [2][S]: x then y
+    elastic: Optional[int] = None                               # ElasticTransform field seed
+
+
 class GpuAugment:
     """Callable: list of decoded samples -> device batch dict (see module docstring)."""
 
@@ -284,47 +309,51 @@ class GpuAugment:
         self._elastic = None       # ElasticTransform displacement [2][S][S] + its scratch
 
     # ------------------------------------------------------------------ draws
+    def draw(self, h0: int, w0: int, img: Optional[np.ndarray] = None) -> SampleDraw:
+        """Everything random about one sample, on the host (no device is touched).  Stream order: the geometric group,
+        the distortion group (synthetic) or the colour and noise OneOfs (regular), the 32-bit noise seed, then
+        (synthetic) the photometric groups.  A Perspective draw deliberately does NOT consume the noise seed (a
+        synthetic geometry pass writes raw RGB and never reads it): recorded batches depend on that, so it stays."""
+        d = self._draw(h0, w0, img)[1]
+        if self.mode == "synthetic":
+            self._draw_synthetic_chain(d, img)
+        return d
+
     def sample_params(self, h0: int, w0: int, img: Optional[np.ndarray] = None) -> AugParams:
-        """Geometry (+ the regular mode's one-pass photometrics) of one sample."""
+        """The geometry stage alone (a synthetic draw's photometric groups are not drawn)."""
         return self._draw(h0, w0, img)[0]
 
+    @staticmethod
+    def _fill(p, h0, w0, nh, nw, ph, pw):
+        p.H0, p.W0, p.new_h, p.new_w, p.pad_h, p.pad_w = h0, w0, nh, nw, ph, pw
+        p.bright = p.contrast = p.sat = 1.0
+        p.mult[0] = p.mult[1] = p.mult[2] = 1.0
+
     def _draw(self, h0, w0, img=None):
-        """-> (AugParams, extra) where extra holds the host-side pieces of the sample's chain: the regular
-        chain's SynthParams + Sharpen kernel when it drew Sharpen or ISONoise, and the GridDistortion maps /
-        ElasticTransform seed of the synthetic distortion group."""
+        """The geometry stage of draw (+ the regular mode's photometrics) -> (AugParams, the SampleDraw that holds it)."""
         S, r = self.S, self.rng
-        nh, nw, ph, pw = letterbox(h0, w0, S)
+        d = SampleDraw(AugParams.identity(h0, w0, S))
+        p = d.geometry
         M = np.eye(3)                              # forward map canvas -> output (pixel-centre coords)
+        H = None                                   # Perspective: output -> the geometric group's output
         bright = contrast = sat = 1.0
         hue, mult, gstd = 0.0, [1.0, 1.0, 1.0], 0.0
-        kdist = 0.0
-        extra = {}
         if self.mode == "synthetic":
             M = self._geometry(M)
             g = _one_of(r, 0.4, [0.3, 0.3, 0.2, 0.15])           # Optical | Grid | Elastic | Perspective
             if g == 0:
-                kdist = r.uniform(-0.3, 0.3) * 0.25                 # distort_limit 0.3 on the normalised radius
+                p.kdist = r.uniform(-0.3, 0.3) * 0.25               # distort_limit 0.3 on the normalised radius
             elif g == 1:                                        # GridDistortion(num_steps 6, distort_limit 0.3)
                 sx = [1 + r.uniform(-0.3, 0.3) for _ in range(7)]
                 sy = [1 + r.uniform(-0.3, 0.3) for _ in range(7)]
-                extra["grid"] = grid_distortion_maps(S, sx, sy, 6)
+                d.grid = np.concatenate(grid_distortion_maps(S, sx, sy, 6))
             elif g == 2:                                        # ElasticTransform(alpha 1, sigma 25)
-                extra["elastic"] = r.getrandbits(32)
+                d.elastic = r.getrandbits(32)
             elif g == 3:                                        # Perspective(scale 0.05-0.1): corner jitter
                 sc = r.uniform(0.05, 0.1)
                 src = np.array([[0, 0], [S, 0], [S, S], [0, S]], np.float64)
                 dst = src + np.array([[r.gauss(0, sc) * S, r.gauss(0, sc) * S] for _ in range(4)])
-                Hm = _homography(dst, src)                      # output -> canvas
-                Mi = np.linalg.inv(M)
-                Tot = Mi @ Hm
-                Tot /= Tot[2, 2]
-                p = AugParams()
-                for i, v in enumerate(list(Tot[0]) + list(Tot[1])):
-                    p.A[i] = float(v)
-                self._fill(p, h0, w0, nh, nw, ph, pw)
-                p.persp[0], p.persp[1] = float(Tot[2, 0]), float(Tot[2, 1])
-                p.raw = 1
-                return p, extra
+                H = _homography(dst, src)
         elif self.mode != "test":
             M = self._geometry(M)
             q = None
@@ -334,7 +363,8 @@ class GpuAugment:
                 sat, hue = r.uniform(0.8, 1.2), r.uniform(-0.2, 0.2)
             elif g == 1:                                        # Sharpen(alpha 0.2-0.5, lightness 0.5-1.0)
                 q = SynthParams.identity()
-                extra["kernel"] = _sharpen_kernel(r.uniform(0.2, 0.5), r.uniform(0.5, 1.0))
+                d.kernel = _sharpen_kernel(r.uniform(0.2, 0.5), r.uniform(0.5, 1.0)).astype(np.float32)
+                q.ksize = 3
             n = _one_of(r, 0.3, [0.5, 0.5, 0.5])                # OneOf(GaussNoise, ISONoise, MultiplicativeNoise) p.3
             if n == 0:
                 gstd = r.uniform(0.2, 0.44)
@@ -347,41 +377,23 @@ class GpuAugment:
                 mult = [r.uniform(0.9, 1.1) for _ in range(3)]
             if q is not None:                                   # Sharpen / ISONoise: the two-stage regular chain
                 q.order = 1
-                q.bright, q.contrast, q.sat, q.hue = bright, contrast, sat, hue
-                q.gauss_std = gstd
-                for i in range(3):
-                    q.mult[i] = mult[i]
-                if "kernel" in extra:
-                    q.ksize = 3
-                extra["chain"] = q
-        Minv = np.linalg.inv(M)
-        p = AugParams()
-        for i, v in enumerate(list(Minv[0]) + list(Minv[1])):
-            p.A[i] = float(v)
-        self._fill(p, h0, w0, nh, nw, ph, pw)
-        p.kdist = kdist
-        p.raw = int(self.mode == "synthetic" or "chain" in extra)
-        p.bright, p.contrast, p.sat, p.hue = bright, contrast, sat, hue
+                d.chain = q
+        Tot = np.linalg.inv(M)                     # output pixel -> canvas
+        if H is not None:                          # (an affine draw keeps inv(M) as it is: "@ identity" would turn its -0.0 into +0.0)
+            Tot = Tot @ H
+            Tot /= Tot[2, 2]
+            p.persp[0], p.persp[1] = float(Tot[2, 0]), float(Tot[2, 1])
+        p.A[:] = [float(v) for v in Tot[:2].ravel()]
+        p.raw = int(self.mode == "synthetic" or d.chain is not None)
         gm = 0.0
         if contrast != 1.0 and img is not None:       # mean grey of the padded canvas after brightness
-            gm = (img[..., 0] * 0.299 + img[..., 1] * 0.587 + img[..., 2] * 0.114).mean() / 255.0
-            gm = min(1.0, gm * bright) * (nh * nw) / (S * S)
-        p.gray_mean = gm
-        if "chain" in extra:
-            extra["chain"].gray_mean = gm
-        for i in range(3):
-            p.mult[i] = mult[i]
-        p.gauss_std = gstd
-        p.seed = r.getrandbits(32)
-        if "chain" in extra:
-            extra["chain"].seed = p.seed
-        return p, extra
-
-    @staticmethod
-    def _fill(p, h0, w0, nh, nw, ph, pw):
-        p.H0, p.W0, p.new_h, p.new_w, p.pad_h, p.pad_w = h0, w0, nh, nw, ph, pw
-        p.bright = p.contrast = p.sat = 1.0
-        p.mult[0] = p.mult[1] = p.mult[2] = 1.0
+            gm = min(1.0, _gray_mean(img) * bright) * (p.new_h * p.new_w) / (S * S)
+        if H is None:
+            p.seed = r.getrandbits(32)
+        for t in filter(None, (p, d.chain)):          # the regular chain carries the one-pass photometrics too
+            t.bright, t.contrast, t.sat, t.hue, t.gray_mean, t.gauss_std, t.seed = bright, contrast, sat, hue, gm, gstd, p.seed
+            t.mult[:] = mult
+        return p, d
 
     def _geometry(self, M):
         """transforms.py:30-39 geometric group (shared by "regular" and "synthetic")."""
@@ -412,18 +424,17 @@ class GpuAugment:
             M = _T(c, c) @ R @ _T(-c, -c) @ M
         return M
 
-    def synth_params(self, img: Optional[np.ndarray] = None):
+    def _draw_synthetic_chain(self, d: SampleDraw, img: Optional[np.ndarray]):
         """The synthetic-mode photometric groups (transforms.py:65-216, albumentations 2.0.8 defaults for the
-        arguments the reference leaves unset): SynthParams + the composed filter taps + the rain drops."""
+        arguments the reference leaves unset) -> d.chain, d.kernel (the composed filter taps) and d.drops."""
         S, r = self.S, self.rng
         q = SynthParams.identity()
         g = _one_of(r, 0.7, [0.7, 0.4, 0.2])                  # ColorJitter | HueSaturationValue | CLAHE
         if g == 0:
             q.bright, q.contrast = r.uniform(0.6, 1.4), r.uniform(0.6, 1.4)
             q.sat, q.hue = r.uniform(0.7, 1.3), r.uniform(-0.2, 0.2)
-            if img is not None:
-                gm = (img[..., 0] * 0.299 + img[..., 1] * 0.587 + img[..., 2] * 0.114).mean() / 255.0
-                q.gray_mean = min(1.0, gm * q.bright)
+            if img is not None:                               # (without draw's letterbox share: intended)
+                q.gray_mean = min(1.0, _gray_mean(img) * q.bright)
         elif g == 1:                                          # uint8 HSV: hue in cv2 units of 2 degrees
             q.hsv_h, q.hsv_s, q.hsv_v = 2.0 * r.uniform(-25, 25), r.uniform(-35, 35) / 255.0, r.uniform(-30, 30) / 255.0
         elif g == 2:                                          # CLAHE(clip_limit 4.0 -> U(1, 4), 8x8 tiles)
@@ -434,8 +445,7 @@ class GpuAugment:
         elif g == 1:
             q.gauss_std = r.uniform(0.25, 0.6)
         elif g == 2:                                          # one multiplier per channel (as the regular mode)
-            for i in range(3):
-                q.mult[i] = r.uniform(0.9, 1.1)
+            q.mult[:] = [r.uniform(0.9, 1.1) for _ in range(3)]
         g = _one_of(r, 0.5, [0.4, 0.3])                       # ImageCompression | Downscale
         if g == 0:
             q.jpeg_quality = r.randint(30, 80)
@@ -459,8 +469,7 @@ class GpuAugment:
         elif g == 3:                                          # ZoomBlur(max_factor 1.03, step_factor 0.01-0.03)
             z = np.arange(1.0, r.uniform(1.0, 1.03), r.uniform(0.01, 0.03))[:4]
             q.zoom_n = len(z)
-            for i, v in enumerate(z):
-                q.zoom[i] = float(v)
+            q.zoom[:len(z)] = [float(v) for v in z]
         g = _one_of(r, 0.05, [0.5, 0.5, 0.3])                 # ToSepia | ToGray | ChannelShuffle
         if g is not None:
             q.color_op = g + 1
@@ -474,7 +483,6 @@ class GpuAugment:
             ker = _conv_full(ker, _sharpen_kernel(r.uniform(0.2, 0.6), r.uniform(0.5, 1.2)))
         elif g == 2:
             q.post_bits = 5
-        drops = None
         g = _one_of(r, 0.15, [0.1, 0.1])                      # RandomSnow | RandomRain
         if g == 0:                                            # bleach, snow_point 0.1-0.3, brightness_coeff 2.5
             q.snow_point, q.snow_coeff = r.uniform(0.1, 0.3), 2.5
@@ -482,18 +490,15 @@ class GpuAugment:
             slant = int(r.uniform(-10, 10))
             n = S * S // 600
             lo, hi = (-slant, S) if slant < 0 else (0, S - slant)
-            drops = np.array([[r.randrange(lo, hi), r.randrange(0, S - 20)] for _ in range(n)], np.int32)
+            d.drops = np.array([[r.randrange(lo, hi), r.randrange(0, S - 20)] for _ in range(n)], np.int32)
             q.rain_n, q.rain_slant, q.rain_len, q.rain_blur = n, slant, 20, 7
             q.rain_color, q.rain_bright = 200.0 / 255.0, 0.7
         q.ksize = ker.shape[0]
         q.seed = r.getrandbits(32)
-        kw = torch.tensor(ker.reshape(-1), dtype=torch.float32).to(self.device, non_blocking=True) if q.ksize > 1 else None
-        dr = torch.from_numpy(drops).to(self.device, non_blocking=True) if drops is not None else None
-        if dr is not None:
-            q.rain_drops = dr.data_ptr()
-        return q, kw, dr
+        d.chain = q
+        d.kernel = ker.astype(np.float32) if q.ksize > 1 else None
 
-    # ------------------------------------------------------------------ device buffers
+    # ------------------------------------------------------------------ device side
     def workspace(self):
         if self._ws is None:
             self._ws = torch.empty(augment_ws_floats(self.S), dtype=torch.float32, device=self.device)
@@ -507,15 +512,31 @@ class GpuAugment:
         lib()("s3od_elastic_field", ctypes.addressof(e), S, self._elastic[1], self._elastic[0], stream())
         return self._elastic[0]
 
-    def _attach(self, p, extra, keep):
-        """Device tables of the distortion group -> AugParams pointers."""
-        if "grid" in extra:
-            gx, gy = extra["grid"]
-            g = torch.from_numpy(np.concatenate([gx, gy]).astype(np.float32)).to(self.device, non_blocking=True)
-            p.grid = g.data_ptr()
-            keep.append(g)
-        if "elastic" in extra:
-            p.elastic = self._elastic_field(extra["elastic"]).data_ptr()
+    def launch(self, d: SampleDraw, img_dev, mask_dev, out_img, out_mask) -> list:
+        """All device work of one drawn sample: uint8 img_dev [H0][W0][3] / mask_dev [H0][W0] -> out_img fp32 [3][S][S]
+        (normalised), out_mask fp32 [S][S].  Uploads d's tables (pageable source, non_blocking, source and copy kept), fills
+        the pointer fields of d's records, runs the geometry pass, then the chain if any.  Returns what must outlive the launches."""
+        S, p, q = self.S, d.geometry, d.chain
+        keep = [img_dev, mask_dev]
+
+        def upload(a):
+            keep.append(torch.from_numpy(np.ascontiguousarray(a)))
+            keep.append(keep[-1].to(self.device, non_blocking=True))
+            return keep[-1]
+
+        if d.grid is not None:
+            p.grid = upload(d.grid).data_ptr()
+        if d.elastic is not None:
+            p.elastic = self._elastic_field(d.elastic).data_ptr()
+        raw = out_img if q is None else torch.empty((3, S, S), dtype=torch.float32, device=self.device)
+        lib()("s3od_augment_sample", img_dev, mask_dev, ctypes.addressof(p), S, raw, out_mask, stream())
+        if q is not None:
+            kw = None if d.kernel is None else upload(d.kernel)
+            q.rain_drops = None if d.drops is None else upload(d.drops).data_ptr()
+            q.ws = self.workspace().data_ptr()
+            lib()("s3od_augment_synthetic", raw, ctypes.addressof(q), kw, S, out_img, stream())
+            keep.append(raw)
+        return keep
 
     def __call__(self, samples: List[Dict[str, np.ndarray]]) -> Dict[str, torch.Tensor]:
         B, S, dev = len(samples), self.S, self.device
@@ -525,27 +546,7 @@ class GpuAugment:
         for b, smp in enumerate(samples):
             img = torch.from_numpy(np.ascontiguousarray(smp["image"], dtype=np.uint8)).pin_memory().to(dev, non_blocking=True)
             msk = torch.from_numpy(np.ascontiguousarray(smp["mask"], dtype=np.uint8)).pin_memory().to(dev, non_blocking=True)
-            h0, w0 = smp["image"].shape[:2]
-            prm, extra = self._draw(h0, w0, smp["image"])
-            self._attach(prm, extra, keep)
-            if self.mode == "synthetic":
-                raw = torch.empty((3, S, S), dtype=torch.float32, device=dev)
-                lib()("s3od_augment_sample", img, msk, ctypes.addressof(prm), S, raw, masks[b], stream())
-                q, kw, dr = self.synth_params(smp["image"])
-                q.ws = self.workspace().data_ptr()
-                lib()("s3od_augment_synthetic", raw, ctypes.addressof(q), kw, S, images[b], stream())
-                keep.append((img, msk, raw, kw, dr))
-                continue
-            if "chain" in extra:                       # regular mode drew Sharpen and / or ISONoise
-                raw = torch.empty((3, S, S), dtype=torch.float32, device=dev)
-                lib()("s3od_augment_sample", img, msk, ctypes.addressof(prm), S, raw, masks[b], stream())
-                q = extra["chain"]
-                q.ws = self.workspace().data_ptr()
-                kw = torch.tensor(extra["kernel"].reshape(-1), dtype=torch.float32).to(dev) if "kernel" in extra else None
-                lib()("s3od_augment_synthetic", raw, ctypes.addressof(q), kw, S, images[b], stream())
-                keep.append((img, msk, raw, kw))
-                continue
-            lib()("s3od_augment_sample", img, msk, ctypes.addressof(prm), S, images[b], masks[b], stream())
-            keep.append((img, msk))
+            d = self.draw(*smp["image"].shape[:2], smp["image"])
+            keep.append(self.launch(d, img, msk, images[b], masks[b]))
         self._inflight = keep                          # keep the uploads alive until the kernels ran
         return {"images": images, "masks": masks}

@@ -48,21 +48,21 @@ def test_synthetic_params_host_logic():
     """Host half of mode="synthetic": every draw is inside the kernel's contract (odd filter <= 15,
     normalised blur taps, valid colour op / posterize / downscale), and the perspective branch gives
     a finite projective map with the same geometry as the mask (one AugParams drives both)."""
-    import torch
     from s3od_amd.data import GpuAugment
     aug = GpuAugment(128, mode="synthetic", device="cpu", seed=3)
     img = np.random.default_rng(0).integers(0, 256, (90, 140, 3), dtype=np.uint8)
     seen_k, seen_op, persp = set(), set(), 0
     seen = set()
     for _ in range(400):
-        q, kw, dr = aug.synth_params(img)
+        drawn = aug.draw(90, 140, img)
+        q, kw, dr, p = drawn.chain, drawn.kernel, drawn.drops, drawn.geometry
         assert q.clahe_clip == 0 or 1.0 <= q.clahe_clip <= 4.0
         assert q.jpeg_quality == 0 or 30 <= q.jpeg_quality <= 80
         assert 0 <= q.zoom_n <= 3 and (q.zoom_n == 0 or (q.zoom[0] == 1.0 and all(1.0 <= q.zoom[i] < 1.03 for i in range(q.zoom_n))))
         assert q.snow_point == 0 or 0.1 <= q.snow_point <= 0.3
         assert (dr is None) == (q.rain_n == 0)
         if dr is not None:                                   # drops stay on the canvas (x + slant too)
-            d = dr.numpy()
+            d = dr
             assert d.shape == (128 * 128 // 600, 2) and -10 < q.rain_slant < 10
             assert (d[:, 0] + min(q.rain_slant, 0) >= 0).all() and (d[:, 0] + max(q.rain_slant, 0) < 128).all()
             assert (d[:, 1] >= 0).all() and (d[:, 1] + 20 < 128).all()
@@ -72,12 +72,11 @@ def test_synthetic_params_host_logic():
         assert q.ksize % 2 == 1 and 1 <= q.ksize <= 15
         assert (kw is None) == (q.ksize == 1)
         if kw is not None:
-            assert kw.numel() == q.ksize ** 2 and torch.isfinite(kw).all() and float(kw.sum()) > 0.3
+            assert kw.size == q.ksize ** 2 and kw.dtype == np.float32 and np.isfinite(kw).all() and float(kw.sum()) > 0.3
         assert 0 <= q.color_op <= 3 and sorted(q.perm) == [0, 1, 2]
         assert q.post_bits in (5, 8) and 0.4 <= q.down <= 1.0 and 0 <= q.n_shadow <= 3
         assert 0.0 <= q.gray_mean <= 1.0
         seen_k.add(q.ksize); seen_op.add(q.color_op)
-        p = aug.sample_params(90, 140, img)
         assert p.raw == 1 and all(np.isfinite(list(p.A))) and np.isfinite(p.persp[0]) and np.isfinite(p.persp[1])
         persp += p.persp[0] != 0 or p.persp[1] != 0
     assert len(seen_k) >= 4 and len(seen_op) >= 2 and persp > 0
@@ -86,9 +85,8 @@ def test_synthetic_params_host_logic():
     a = GpuAugment(128, mode="synthetic", device="cpu", seed=11)
     b = GpuAugment(128, mode="synthetic", device="cpu", seed=11)
     for _ in range(20):
-        qa, _, _ = a.synth_params(img); qb, _, _ = b.synth_params(img)
-        qa.rain_drops = qb.rain_drops = None
-        assert bytes(qa) == bytes(qb)
+        da, db = a.draw(90, 140, img), b.draw(90, 140, img)
+        assert bytes(da.chain) == bytes(db.chain) and bytes(da.geometry) == bytes(db.geometry)
 
 
 def test_synthetic_mode_rejects_sizes_clahe_cannot_tile():
@@ -108,8 +106,7 @@ def test_multiplicative_noise_draws_one_multiplier_per_channel():
     img = np.zeros((64, 64, 3), np.uint8)
     seen = 0
     for _ in range(300):
-        q, _, _ = aug.synth_params(img)
-        m = list(q.mult)
+        m = list(aug.draw(64, 64, img).chain.mult)
         if m != [1.0, 1.0, 1.0]:
             assert len(set(m)) == 3 and all(0.9 <= v <= 1.1 for v in m)
             seen += 1
@@ -136,19 +133,73 @@ def test_regular_mode_draws_sharpen_and_iso_chain():
     aug = GpuAugment(64, mode="regular", device="cpu", seed=5)
     n, sharpen, iso = 4000, 0, 0
     for _ in range(n):
-        p, extra = aug._draw(50, 60)
-        q = extra.get("chain")
+        d = aug.draw(50, 60)
+        p, q = d.geometry, d.chain
         if q is not None:
             assert p.raw == 1 and q.order == 1
             sharpen += q.ksize == 3
             iso += q.iso_intensity > 0
+            assert (d.kernel is None) == (q.ksize == 1)
             if q.ksize == 3:
-                assert extra["kernel"].shape == (3, 3)
+                assert d.kernel.shape == (3, 3)
             if q.iso_intensity > 0:
                 assert 0.1 <= q.iso_intensity <= 0.5 and 0.01 <= q.iso_color_shift <= 0.05
         else:
             assert p.raw == 0
     assert abs(sharpen / n - 0.5 * 0.3) < 0.025 and abs(iso / n - 0.3 / 3) < 0.02, (sharpen / n, iso / n)
+
+
+@pytest.mark.parametrize("mode", ["regular", "synthetic"])
+def test_draw_stream_matches_recorded_draws(mode):
+    """GpuAugment.draw reproduces, byte for byte, the draws recorded in tests/golden/augment_draws.npz at commit
+    2bb4301 (the last one with the (AugParams, extra) / (q, kw, dr) draw API; recorded with its _draw and
+    synth_params in __call__'s order): GpuAugment(96, mode, device="cpu", seed=s), four samples per seed of one
+    72x96 image from np.random.RandomState(0), regular seeds 0..7, synthetic seeds 0..15.  Per sample: the raw
+    bytes of AugParams and SynthParams (pointer fields zero), the float32 filter kernel, the rain drops, the
+    GridDistortion maps and the ElasticTransform seed.  Each member the file must exercise occurs at least twice."""
+    import ctypes
+    from pathlib import Path
+    from s3od_amd.data import AugParams, GpuAugment, SynthParams
+    G = np.load(Path(__file__).parent / "golden" / "augment_draws.npz")
+    k = mode[:3]
+    img = np.random.RandomState(0).randint(0, 256, (72, 96, 3)).astype(np.uint8)
+    seen = {}
+    count = lambda **kw: seen.update({n: seen.get(n, 0) + bool(on) for n, on in kw.items()})
+    i = 0
+    for seed in range(8 if mode == "regular" else 16):
+        aug = GpuAugment(96, mode, device="cpu", seed=seed)
+        for _ in range(4):
+            d = aug.draw(72, 96, img)
+            tag = f"{mode} seed {seed} record {i}"
+            assert bytes(d.geometry) == G[f"{k}_aug"][i].tobytes(), tag
+            assert (d.chain is not None) == bool(G[f"{k}_has_chain"][i]), tag
+            if d.chain is not None:
+                assert bytes(d.chain) == G[f"{k}_chain"][i].tobytes(), tag
+            ker = G[f"{k}_kernel"][G[f"{k}_kernel_off"][i]:G[f"{k}_kernel_off"][i + 1]]
+            assert (d.kernel is None) == (ker.size == 0), tag
+            if d.kernel is not None:
+                assert d.kernel.dtype == np.float32 and d.kernel.tobytes() == ker.tobytes(), tag
+            drops = G[f"{k}_drops"][G[f"{k}_drops_off"][i]:G[f"{k}_drops_off"][i + 1]]
+            assert (d.drops is None) == (len(drops) == 0), tag
+            if d.drops is not None:
+                assert d.drops.dtype == np.int32 and d.drops.tobytes() == drops.tobytes(), tag
+            assert (d.grid is not None) == bool(G[f"{k}_has_grid"][i]), tag
+            if d.grid is not None:
+                assert d.grid.dtype == np.float32 and d.grid.tobytes() == G[f"{k}_grid"][i].tobytes(), tag
+            assert (-1 if d.elastic is None else d.elastic) == int(G[f"{k}_elastic"][i]), tag
+            p, q = d.geometry, d.chain
+            if mode == "synthetic":
+                count(perspective=p.persp[0] != 0 or p.persp[1] != 0, kdist=p.kdist != 0, grid=d.grid is not None,
+                      elastic=d.elastic is not None, clahe=q.clahe_clip > 0, hsv=q.hsv_h != 0, iso=q.iso_intensity > 0,
+                      jpeg=q.jpeg_quality > 0, downscale=q.down < 1, shadow=q.n_shadow > 0, rbc=q.rbc_alpha != 1,
+                      zoom=q.zoom_n > 0, colour_op=q.color_op > 0, posterize=q.post_bits < 8, snow=q.snow_point > 0,
+                      rain=q.rain_n > 0, filter13=q.ksize >= 13)
+            else:
+                count(sharpen_chain=q is not None and q.ksize == 3, iso_chain=q is not None and q.iso_intensity > 0,
+                      one_pass_jitter=q is None and p.bright != 1, one_pass_gauss=q is None and p.gauss_std > 0)
+            i += 1
+    assert i == len(G[f"{k}_aug"]) and ctypes.sizeof(AugParams) == G[f"{k}_aug"].shape[1] and ctypes.sizeof(SynthParams) == G[f"{k}_chain"].shape[1]
+    assert all(n >= 2 for n in seen.values()), seen
 
 
 def test_jpeg_restatement_matches_libjpeg():
@@ -174,7 +225,7 @@ def test_jpeg_restatement_matches_libjpeg():
             assert abs(lo - ll) <= 0.05 * ll, (S, q, lo, ll)
 
 
-# ------------------------------------------------------------------ host composition of the warp (GpuAugment._geometry / _draw)
+# ------------------------------------------------------------------ host composition of the warp (GpuAugment._geometry / draw)
 class _Script:
     """random.Random stand-in: every draw returns the next scripted value, whatever its distribution, so a
     test walks one branch of the host code at a time."""
@@ -219,10 +270,12 @@ def _geo(script):
 def _draw_A(script, mode="regular"):
     from s3od_amd.data import GpuAugment
     aug = GpuAugment(_S, mode=mode, device="cpu", seed=0)
+    if mode == "synthetic":                          # the photometric groups follow: eight OneOf gates taken by none, the chain's seed
+        script = script + [_NO] * 8 + [4321]
     aug.rng = _Script(script)
-    p, extra = aug._draw(72, 96)
+    d = aug.draw(72, 96)
     assert not aug.rng.values
-    return p
+    return d.geometry
 
 
 def _apply(M, pts):

@@ -183,7 +183,7 @@ def _geometry(S, p_mod):
     img = r.integers(0, 256, (S - 10, S, 3), dtype=np.uint8)
     msk = (r.random((S - 10, S)) > 0.5).astype(np.uint8) * 255
     aug = GpuAugment(S, mode="test")
-    p = aug.sample_params(S - 10, S)
+    p = aug.draw(S - 10, S).geometry
     p.raw = 1
     ti, tm = torch.from_numpy(img).cuda(), torch.from_numpy(msk).cuda()
     base = torch.empty(3, S, S, device="cuda"); bm = torch.empty(S, S, device="cuda")

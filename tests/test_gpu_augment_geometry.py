@@ -77,9 +77,8 @@ def _source(h, w):
 def _params(h0, w0, S, fwd, persp=(0.0, 0.0), kdist=0.0):
     """AugParams of the forward map `fwd` (canvas -> output, pixel-centre coordinates), inverted here;
     persp: the denominator row applied to the output pixel before the inverse (Perspective)."""
-    from s3od_amd.data import AugParams, GpuAugment, letterbox
-    p = AugParams()
-    GpuAugment._fill(p, h0, w0, *letterbox(h0, w0, S))
+    from s3od_amd.data import AugParams
+    p = AugParams.identity(h0, w0, S)
     Tot = np.linalg.inv(fwd) @ np.array([[1, 0, 0], [0, 1, 0], [persp[0], persp[1], 1.0]])
     Tot /= Tot[2, 2]
     for i, v in enumerate(list(Tot[0]) + list(Tot[1])):

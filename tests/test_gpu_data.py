@@ -25,9 +25,8 @@ def _sample(h, w, seed=0):
 
 
 def _ref_test_mode(smp, S):
-    from s3od_amd.data import AugParams, GpuAugment, letterbox
-    p = AugParams()
-    GpuAugment._fill(p, *smp["mask"].shape, *letterbox(*smp["mask"].shape, S))
+    from s3od_amd.data import AugParams
+    p = AugParams.identity(*smp["mask"].shape, S)
     canvas, mcan = AO.letterbox_canvas(smp["image"], smp["mask"], p, S)
     return (canvas - MEAN[:, None, None]) / STD[:, None, None], mcan
 
@@ -54,7 +53,7 @@ def test_flip_and_rot90_are_exact_permutations():
     msk = torch.from_numpy(smp["mask"]).cuda()
 
     def run(Minv):
-        p = aug.sample_params(50, 64)
+        p = aug.draw(50, 64).geometry
         for i, v in enumerate(list(Minv[0]) + list(Minv[1])):
             p.A[i] = float(v)
         oi = torch.empty((3, S, S), device="cuda"); om = torch.empty((S, S), device="cuda")
@@ -98,7 +97,7 @@ def test_synthetic_identity_chain_equals_test_mode():
     smp = _sample(80, 120, 4)
     base = GpuAugment(S, mode="test")([smp])
     aug = GpuAugment(S, mode="test")
-    p = aug.sample_params(80, 120, smp["image"])
+    p = aug.draw(80, 120, smp["image"]).geometry
     p.raw = 1
     img = torch.from_numpy(smp["image"]).cuda(); msk = torch.from_numpy(smp["mask"]).cuda()
     raw = torch.empty(3, S, S, device="cuda"); om = torch.empty(S, S, device="cuda"); out = torch.empty(3, S, S, device="cuda")
@@ -170,28 +169,19 @@ E2E_SOURCES = [(108, 144), (144, 108), (36, 48), (72, 96)]
 E2E_SEEDS = {"regular": (0, 1, 2), "synthetic": (12, 19, 38)}       # chosen on the CPU: see _drawn and the test's last asserts
 
 
-def _replay(mode, seed, smps, S=96):
-    """The draws of GpuAugment(S, mode, seed) for these samples, from a second instance: _draw and
-    synth_params are host-only and consume the same stream in the same order as __call__."""
+def _replay(mode, seed, smps, S=96, device="cpu"):
+    """The draws of GpuAugment(S, mode, seed) for these samples, from a second instance: draw is host-only
+    and __call__ makes exactly one per sample, in order."""
     from s3od_amd.data import GpuAugment
-    rep = GpuAugment(S, mode=mode, device="cpu", seed=seed)
-    draws = []
-    for smp in smps:
-        p, extra = rep._draw(*smp["image"].shape[:2], smp["image"])
-        q, ker = extra.get("chain"), extra.get("kernel")
-        if mode == "synthetic":
-            q, kw, _ = rep.synth_params(smp["image"])
-            ker = kw.numpy().astype(np.float64).reshape(q.ksize, q.ksize) if kw is not None else None
-        elif ker is not None:
-            ker = ker.astype(np.float32).astype(np.float64)
-        draws.append((p, extra, q, ker))
-    return draws
+    rep = GpuAugment(S, mode=mode, device=device, seed=seed)
+    return rep, [rep.draw(*smp["image"].shape[:2], smp["image"]) for smp in smps]
 
 
 def _drawn(draws):
     """Which of the members the end-to-end test must see were drawn."""
     seen = set()
-    for p, extra, q, ker in draws:
+    for d in draws:
+        p, q = d.geometry, d.chain
         A = np.array(list(p.A))
         if np.abs(A - np.rint(A)).max() > 1e-3:
             seen.add("fractional_affine")
@@ -250,14 +240,16 @@ def test_drawn_batch_matches_oracle(mode):
     for seed in E2E_SEEDS[mode]:
         out = GpuAugment(S, mode=mode, seed=seed)(smps)
         torch.cuda.synchronize()
-        draws = _replay(mode, seed, smps)
+        _, draws = _replay(mode, seed, smps)
         seen |= _drawn(draws)
-        for b, (smp, (p, extra, q, ker)) in enumerate(zip(smps, draws)):
+        for b, (smp, d) in enumerate(zip(smps, draws)):
             tag = f"{mode} seed {seed} sample {b}"
-            grid = np.concatenate(extra["grid"]).astype(np.float32) if "grid" in extra else None
+            p, q = d.geometry, d.chain
+            ker = d.kernel.astype(np.float64) if d.kernel is not None else None
+            grid = d.grid
             keep, fld = [], None
-            if "elastic" in extra:                      # the device generator's field (it has its own parity test)
-                e = elastic_params(extra["elastic"])
+            if d.elastic is not None:                   # the device generator's field (it has its own parity test)
+                e = elastic_params(d.elastic)
                 tmp = torch.empty(2, S, S, device="cuda"); fld = torch.empty(2, S, S, device="cuda")
                 lib()("s3od_elastic_field", ctypes.addressof(e), S, tmp, fld, stream())
                 torch.cuda.synchronize()
@@ -312,3 +304,29 @@ def test_drawn_batch_matches_oracle(mode):
     assert want <= seen, (want - seen)
     assert full >= 6, full                              # most samples are compared through to the batch image
     assert not fails, "\n".join(fails)
+
+
+def test_batch_equals_launch_of_replayed_draws():
+    """__call__ is the loop around draw and launch, and nothing else: for one regular and one synthetic seed
+    (chosen on the CPU: a Sharpen chain, an ISONoise chain, one-pass samples; rain, an elastic field, 3x3 and 7x7
+    filters), launch of the replayed draws into fresh NaN-filled buffers, one sample at a time, gives the
+    batch's images and masks bit for bit.  ISONoise samples are left out: their float64 lightness sums go through
+    atomics whose order varies from run to run (test_drawn_batch_matches_oracle covers them)."""
+    S = 96
+    smps = [_sample(h, w, 10 + i) for i, (h, w) in enumerate(E2E_SOURCES)]
+    compared = 0
+    for mode, seed in (("regular", E2E_SEEDS["regular"][1]), ("synthetic", E2E_SEEDS["synthetic"][2])):
+        from s3od_amd.data import GpuAugment
+        out = GpuAugment(S, mode=mode, seed=seed)(smps)
+        torch.cuda.synchronize()
+        rep, draws = _replay(mode, seed, smps, device="cuda")
+        for b, (smp, d) in enumerate(zip(smps, draws)):
+            if d.chain is not None and d.chain.iso_intensity > 0:
+                continue
+            oi = torch.full((3, S, S), float("nan"), device="cuda"); om = torch.full((S, S), float("nan"), device="cuda")
+            keep = rep.launch(d, torch.from_numpy(smp["image"]).cuda(), torch.from_numpy(smp["mask"]).cuda(), oi, om)
+            torch.cuda.synchronize()
+            del keep
+            assert torch.equal(oi, out["images"][b]) and torch.equal(om, out["masks"][b]), f"{mode} seed {seed} sample {b}"
+            compared += 1
+    assert compared >= 6, compared

@@ -15,7 +15,8 @@ the first side, which cannot be counting its vector-memory queue by hand.
 
 Each side's csrc/ is compiled with the flags the Makefile gives that file.  The texts compared are the kernel bodies
 without comments, debug and section directives and blank lines, with the kernel's own mangled name and the per-file function
-numbers of local labels replaced (a kernel whose function or template parameters changed pairs with its one namesake).
+numbers of local labels replaced, and the enclosing function's name dropped from the symbol of a function-local constant
+table, which moves when the table moves into a shared helper (its contents are not compared) (a kernel whose function or template parameters changed pairs with its one namesake).
 """
 import re
 import subprocess
@@ -86,6 +87,7 @@ def compile_rev(src, rev, tmp):
             out[name] = ("\n".join(body).replace(name, "KERNEL"), res[name])
             name = None
         elif name is not None:
+            line = re.sub(r"__const\.\w+\.(\w+)", r"__const.\1", line)     # a function-local table is named after its function
             body.append(re.sub(r"\.L(BB|tmp|func_\w+?)\d+", r".L\1", line))
     return out
 

@@ -13,7 +13,8 @@ glue (every entry point of decoder_ops.hip / vit_ops.hip / loss.hip that reduces
 shapes and at the training step's shapes: give the first build twice, `glue parent parent new`, and each output of the
 third is judged by whether the first two agree bit for bit -- then it must too -- or only to summation order, as the sums
 through fp32 atomics do -- then rel-L2 1e-5, or the first two's own scatter where that is larger; the training
-shapes are also timed).
+shapes are also timed);
+augment (the entries of data_ops.hip, `augment parent parent new` like glue: see augment()).
 """
 import ctypes
 import os
@@ -410,6 +411,156 @@ def glue(libs, rounds):
     return bad
 
 
+def augment(libs, rounds):
+    """The training-augmentation entries of data_ops.hip on shared seeded inputs: s3od_augment_sample (one pass with jitter and
+    noise; raw with grid + elastic + perspective + radial distortion), s3od_elastic_field, and s3od_augment_synthetic once per
+    member and once with everything on, for order 0 and order 1.  Compared at S = 96 and 264, timed at the training canvas
+    S = 1024.  Give the first build twice (`augment parent parent new`): an output of the third must equal the first's bit for
+    bit where the first two agree bit for bit, and be within their rel-L2 scatter where they differ (ISONoise's float64
+    sums go through atomics); its median time must not lie above the spread (min .. max over the rounds) of the first two."""
+    import math
+    import numpy as np
+    from s3od_amd.data import (AugParams, SynthParams, _conv_full, _disk_kernel, _gauss_kernel, _sharpen_kernel,
+                               elastic_params, grid_distortion_maps)
+    st = stream()
+    cmp = lambda a, b: "equal" if torch.equal(a, b) else f"{float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-300)):.2e}"
+    bad = slow = 0
+
+    def members(S):
+        """-> [(name, {SynthParams field: value}, filter kernel or None)] for both orders"""
+        r = np.random.RandomState(5)
+        blur = _conv_full(_gauss_kernel(5), _sharpen_kernel(0.4, 0.8))                       # 7x7
+        big = _conv_full(_disk_kernel(6, 0.2), _sharpen_kernel(0.3, 1.0))                    # 15x15
+        shadow = [[float(v) for xy in zip(r.randint(0, S, 5), r.randint(S // 10, S, 5)) for v in xy] for _ in range(3)]
+        slant = -6
+        drops = np.stack([r.randint(-slant, S, S * S // 600), r.randint(0, S - 20, S * S // 600)], 1).astype(np.int32)
+        one = {"jitter": dict(bright=0.8, contrast=1.3, sat=1.2, hue=0.07, gray_mean=0.4), "hsv": dict(hsv_h=30.0, hsv_s=0.1, hsv_v=-0.08),
+               "clahe": dict(clahe_clip=3.0), "iso": dict(iso_intensity=0.25, iso_color_shift=0.02), "gauss": dict(gauss_std=0.4),
+               "mult": dict(mult=[0.92, 1.05, 1.08]), "jpeg": dict(jpeg_quality=45), "down": dict(down=0.55),
+               "shadow": dict(n_shadow=3, shadow=shadow, shadow_dim=0.5), "rbc": dict(rbc_alpha=1.2, rbc_beta=-0.1),
+               "filter7": dict(ksize=7), "filter15": dict(ksize=15), "zoom": dict(zoom_n=3, zoom=[1.0, 1.01, 1.02]),
+               "sepia": dict(color_op=1), "gray": dict(color_op=2), "shuffle": dict(color_op=3, perm=[2, 0, 1]),
+               "posterize": dict(post_bits=5), "snow": dict(snow_point=0.2, snow_coeff=2.5),
+               "rain": dict(rain_n=len(drops), rain_slant=slant, rain_len=20, rain_blur=7, rain_color=200 / 255, rain_bright=0.7)}
+        everything = {k: v for n, m in one.items() if n not in ("filter15", "gray", "shuffle") for k, v in m.items()}
+        reg = {"sharpen": dict(ksize=3), "jitter": one["jitter"], "iso": one["iso"], "gauss": one["gauss"], "mult": one["mult"]}
+        reg["everything"] = {k: v for m in reg.values() for k, v in m.items()}
+        kern = lambda m: {3: _sharpen_kernel(0.4, 0.8), 7: blur, 15: big}.get(m.get("ksize"))
+        out = [(f"order 0 {n}", dict(m, seed=1234 + i), kern(m)) for i, (n, m) in enumerate({**one, "everything": everything}.items())]
+        out += [(f"order 1 {n}", dict(m, order=1, seed=4321 + i), kern(m)) for i, (n, m) in enumerate(reg.items())]
+        return out, drops
+
+    def params(S, fields, drops_dev, ws):
+        q = SynthParams.identity()
+        for k, v in fields.items():
+            if k == "shadow":
+                for t, poly in enumerate(v):
+                    for i, c in enumerate(poly):
+                        q.shadow[t][i] = c
+            elif isinstance(v, list):
+                for i, c in enumerate(v):
+                    getattr(q, k)[i] = c
+            else:
+                setattr(q, k, v)
+        q.rain_drops, q.ws = drops_dev.data_ptr() if q.rain_n else None, ws.data_ptr()
+        return q
+
+    for S, is_timed in ((96, False), (264, False), (1024, True)):
+        g = torch.Generator(device="cuda").manual_seed(S)
+        h0, w0 = 3 * S // 4, S
+        img = torch.randint(0, 256, (h0, w0, 3), device="cuda", generator=g, dtype=torch.uint8)
+        msk = (torch.rand(h0, w0, device="cuda", generator=g) > 0.5).to(torch.uint8) * 255
+        raw0 = torch.nn.functional.interpolate(torch.rand(1, 3, S // 4, S // 4, device="cuda", generator=g), size=(S, S), mode="bilinear")[0].contiguous()
+        th, c = math.radians(9.0), S / 2
+        T = lambda tx, ty: np.array([[1, 0, tx], [0, 1, ty], [0, 0, 1]], np.float64)
+        R = np.array([[math.cos(th), math.sin(th), 0], [-math.sin(th), math.cos(th), 0], [0, 0, 1]])
+        fwd = np.diag([96 / 83, 96 / 91, 1.0]) @ T(-5.0 * S / 96, -2.0 * S / 96) @ T(c, c) @ R @ T(-c, -c)
+
+        def geometry(persp):
+            p = AugParams.identity(h0, w0, S)
+            Tot = np.linalg.inv(fwd) @ np.array([[1, 0, 0], [0, 1, 0], [persp[0], persp[1], 1.0]])
+            Tot /= Tot[2, 2]
+            for i, v in enumerate(list(Tot[0]) + list(Tot[1])):
+                p.A[i] = float(v)
+            p.persp[0], p.persp[1] = float(Tot[2, 0]), float(Tot[2, 1])
+            return p
+        one_pass = geometry((0.0, 0.0))
+        one_pass.bright, one_pass.contrast, one_pass.sat, one_pass.hue, one_pass.gray_mean = 0.8, 1.3, 1.2, 0.07, 0.3
+        one_pass.mult[0], one_pass.mult[1], one_pass.mult[2], one_pass.gauss_std, one_pass.seed = 0.92, 1.05, 1.08, 0.3, 99
+        rs = np.random.RandomState(11)
+        grid = torch.from_numpy(np.concatenate(grid_distortion_maps(S, 1 + rs.uniform(-0.3, 0.3, 7), 1 + rs.uniform(-0.3, 0.3, 7), 6))
+                                .astype(np.float32)).cuda()
+        ep = elastic_params(777, alpha=3.0)
+        field, tmp0 = torch.empty(2, S, S, device="cuda"), torch.empty(2, S, S, device="cuda")
+        libs[0]("s3od_elastic_field", ctypes.addressof(ep), S, tmp0, field, st)                  # shared input of the raw pass
+        distorted = geometry((0.3 / S, -0.2 / S))
+        distorted.kdist, distorted.raw, distorted.grid, distorted.elastic = 0.05, 1, grid.data_ptr(), field.data_ptr()
+        chain, drops = members(S)
+        drops_dev = torch.from_numpy(drops).cuda()
+        nws = ctypes.c_long(0)
+        libs[0]("s3od_augment_ws_floats", S, ctypes.addressof(nws))
+        cases = []
+
+        # every build of a case runs on the SAME buffers (outputs are cloned after its run): with buffers of their own, two
+        # handles of one library measured up to 1.5 % apart on the 20 .. 100 us entries
+        def sample(p):
+            o = {"img": torch.empty(3, S, S, device="cuda"), "mask": torch.empty(S, S, device="cuda")}
+            return lambda L: ((lambda: L("s3od_augment_sample", img, msk, ctypes.addressof(p), S, o["img"], o["mask"], st)), o)
+
+        def elastic():
+            o, tmp = {"field": torch.empty(2, S, S, device="cuda")}, torch.empty(2, S, S, device="cuda")
+            return lambda L: ((lambda: L("s3od_elastic_field", ctypes.addressof(ep), S, tmp, o["field"], st)), o)
+
+        def synthetic(fields, ker):
+            kw = torch.tensor(ker.reshape(-1), dtype=torch.float32, device="cuda") if ker is not None else None
+            o, raw, ws = {"out": torch.empty(3, S, S, device="cuda")}, torch.empty_like(raw0), torch.zeros(nws.value, device="cuda")
+            q = params(S, fields, drops_dev, ws)
+
+            def mk(L):
+                def f():
+                    raw.copy_(raw0)                                                               # (the entry uses raw as scratch)
+                    q.ws = ws.data_ptr()                                                          # (and keeps ws alive: q holds an address only)
+                    L("s3od_augment_synthetic", raw, ctypes.addressof(q), kw, S, o["out"], st)
+                return f, o
+            return mk
+        cases += [("augment_sample one pass", sample(one_pass)), ("augment_sample raw, distorted", sample(distorted)), ("elastic_field", elastic())]
+        cases += [(f"augment_synthetic {n}", synthetic(m, k)) for n, m, k in chain]
+        for name, mk in cases:
+            runs, outs = [mk(L) for L in libs], []
+            for f, o in runs:
+                for t in o.values():
+                    t.fill_(float("nan"))
+                f()
+                torch.cuda.synchronize()
+                outs.append({k: t.clone() for k, t in o.items()})
+            line = f"S{S} {name}:"
+            for k in outs[0]:
+                res = [cmp(o[k], outs[0][k]) for o in outs[1:]]
+                line += f" {k} " + " / ".join(res)
+                if len(res) == 2:                   # parent, parent, new
+                    pp, pn = res
+                    ok = pn == "equal" if pp == "equal" else (pn == "equal" or float(pn) <= float(pp))
+                    line += "" if ok else " <-- MISS"
+                    bad += not ok
+            if is_timed:
+                ts = [[] for _ in libs]
+                for r in range(rounds):                                     # the later slots of a round measure ~1 % slower on
+                    for i in [(r + j) % len(libs) for j in range(len(libs))]:     # 20 us entries: every build takes every slot
+                        ts[i].append(timed(runs[i][0], 20) * 1e3)
+                med = [sorted(t)[len(t) // 2] for t in ts]
+                line += " | us " + " | ".join(f"lib{i} med {m:8.1f} ({min(t):8.1f} .. {max(t):8.1f})" for i, (m, t) in enumerate(zip(med, ts)))
+                if len(libs) == 3:
+                    lo, hi = min(ts[0] + ts[1]), max(ts[0] + ts[1])
+                    verdict = "within" if lo <= med[2] <= hi else ("below" if med[2] < lo else "ABOVE")
+                    line += f" | parents' spread {lo:.1f} .. {hi:.1f}: new median {verdict}"
+                    slow += verdict == "ABOVE"
+            print(line, flush=True)
+            del runs
+    print(f"augment: {bad} outputs MISS the rule (equal where the first two builds agree bit for bit, within their rel-L2 scatter "
+          f"elsewhere); {slow} timed entries with the last build's median above the spread of the first two")
+    return bad + slow
+
+
 if __name__ == "__main__":
     what, paths = sys.argv[1], sys.argv[2:]
     libs = [Lib(p) for p in paths]
@@ -422,3 +573,5 @@ if __name__ == "__main__":
         lin(libs, rounds)
     elif what == "glue":
         sys.exit(1 if glue(libs, rounds) else 0)
+    elif what == "augment":
+        sys.exit(1 if augment(libs, rounds) else 0)
