@@ -66,6 +66,19 @@ __global__ void canvas_fill_kernel(float* out, int S) {
   out[i] = imagenet_norm(0.f, c);
 }
 
+// ---------------------------------------------------------------- horizontal mirror (cv2.flip(image, 1))
+// dst[y][x][c] = src[y][W - 1 - x][c] on packed uint8 HWC: one byte per thread and grid-stride step, so the stores are
+// coalesced and the loads run backwards pixel by pixel within the same row segment
+__global__ void __launch_bounds__(256) mirror_u8_kernel(const unsigned char* __restrict__ src, long N, int W, int C,
+                                                        unsigned char* __restrict__ dst) {
+  const long WC = (long)W * C;
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < N; i += gridDim.x * 256L) {
+    const long row = i / WC;
+    const int r = (int)(i - row * WC), x = r / C, c = r - x * C;
+    dst[i] = src[row * WC + (long)(W - 1 - x) * C + c];
+  }
+}
+
 // ---------------------------------------------------------------- batched entries: descriptor tables
 // One descriptor per image; the tables are packed arrays in device memory (the host keeps a copy for the argument
 // checks).  include/s3od_hip.h carries these definitions; s3od_amd/infer_many.py mirrors them with ctypes.
@@ -599,6 +612,18 @@ int s3od_preprocess(const void* img, int H0, int W0, int new_h, int new_w, int p
   hipLaunchKernelGGL(preprocess_kernel, dim3(cdiv(new_w, 256), new_h), dim3(256), 0, st, (const unsigned char*)img, H0, W0,
                      new_h, new_w, pad_h, pad_w, S, out);
   return s3od_check_launch("preprocess");
+}
+
+// src, dst: device uint8 [H][W][C], contiguous, C in 1..4, src != dst; dst[y][x][c] = src[y][W-1-x][c] (the horizontal
+// mirror of the source image, taken before the letterbox)
+int s3od_mirror_u8(const void* src, int H, int W, int C, void* dst, void* stream) {
+  S3OD_REQUIRE(src != nullptr && dst != nullptr && src != dst, "mirror_u8: source / destination missing or the same buffer");
+  S3OD_REQUIRE(H >= 1 && W >= 1 && C >= 1 && C <= 4, "mirror_u8: %d x %d x %d outside H, W >= 1, C in 1..4", H, W, C);
+  S3OD_REQUIRE((long)W * C <= 2147483647L, "mirror_u8: row longer than 2^31 - 1 bytes");
+  const long N = (long)H * W * C;
+  hipLaunchKernelGGL(mirror_u8_kernel, dim3((unsigned)std::min<long>(4096, (N + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned char*)src, N, W, C, (unsigned char*)dst);
+  return s3od_check_launch("mirror_u8");
 }
 
 // logits: fp32 [NM][LH][LW] (one image, NM masks; LH x LW = S x S, or S x 16*floor(new_w/16) for the

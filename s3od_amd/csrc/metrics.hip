@@ -436,6 +436,149 @@ __global__ void __launch_bounds__(256) final_kernel(const double* __restrict__ a
 
 inline int sweep_grid(long N) { return (int)std::min<long>(2048, std::max<long>(1, (N + TB - 1) / TB)); }
 
+// ---------------------------------------------------------------- flip-consistency scores
+// mine_samples.py:16-51 (eval_sample: three sm_only steps in a row on the same tensors) and
+// consistency_filter.py:49-95 (three binary IoUs) of one image in two sweeps and a finishing block.  a is the soft
+// mask of the image, b(y, x) = bm[y][W - 1 - x] the soft mask of its mirror read back through the mirror, gt the
+// ground truth.  The pairs are (pred, mask) = (a, gt), (b, gt') and (a, b), where gt' is gt as step 1 left it.
+//
+// accumulator slots of sweep 1 (doubles at the start of the workspace)
+enum {
+  F_YSUM = 0, F_N1, F_CX, F_CY,                        // gt: raw sum; count and centroid moments of gt >= 0.5
+  F_AFG1, F_AFG2, F_ABG1, F_ABG2,                      // object moments of a on / off that foreground
+  F_BFG1, F_BFG2, F_BBG1, F_BBG2,                      // the same of b
+  F_ASUM, F_BSUM,                                      // raw sums of a and of b (b's is also pair 3's mask sum)
+  F_NB1, F_BCX, F_BCY,                                 // count and centroid moments of b >= 0.5
+  F_CFG1, F_CFG2, F_CBG1, F_CBG2,                      // object moments of a on / off b >= 0.5
+  F_I_AG, F_U_AG, F_I_BG, F_U_BG, F_I_AB, F_U_AB,      // intersection / union counts of the three IoU pairs
+  F_NS1
+};
+// sweep 2: [4][8] = n, g, a, aa, ag, b, bb, bg per quadrant about gt's centroid (g = gt >= 0.5), then
+// [4][5] = n, m, a, aa, am per quadrant about b's centroid (m = b >= 0.5)
+constexpr int FQ_G = 32;
+constexpr int FQ_B = FQ_G + 32;
+constexpr int FQ_N = 32 + 20;
+constexpr int F_WORDS = 96;
+
+__global__ void __launch_bounds__(TB) flip_stats_kernel(const float* __restrict__ a, const float* __restrict__ bm,
+                                                        const float* __restrict__ gt, long N, int W, float thr,
+                                                        double* __restrict__ acc) {
+  double v[F_NS1];
+#pragma unroll
+  for (int j = 0; j < F_NS1; j++) v[j] = 0.0;
+  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+    const long y = i / W, x = i - y * W;
+    const float pa = a[i], pb = bm[i + (W - 1 - 2 * x)], m = gt[i];     // b(y, x) = bm[y][W - 1 - x]
+    const double ad = pa, bd = pb;
+    const double qa = (double)(1.f - pa), qb = (double)(1.f - pb);      // bg = 1 - pred in float32, as stats_kernel
+    v[F_YSUM] += (double)m; v[F_ASUM] += ad; v[F_BSUM] += bd;
+    if (m >= 0.5f) {
+      v[F_N1] += 1.0; v[F_CX] += (double)x; v[F_CY] += (double)y;
+      v[F_AFG1] += ad; v[F_AFG2] += ad * ad; v[F_BFG1] += bd; v[F_BFG2] += bd * bd;
+    } else {
+      v[F_ABG1] += qa; v[F_ABG2] += qa * qa; v[F_BBG1] += qb; v[F_BBG2] += qb * qb;
+    }
+    if (pb >= 0.5f) {
+      v[F_NB1] += 1.0; v[F_BCX] += (double)x; v[F_BCY] += (double)y;
+      v[F_CFG1] += ad; v[F_CFG2] += ad * ad;
+    } else {
+      v[F_CBG1] += qa; v[F_CBG2] += qa * qa;
+    }
+    const bool ta = pa > thr, tb = pb > thr, tg = m > 0.5f;              // calculate_iou's binarisation
+    v[F_I_AG] += (ta && tg) ? 1.0 : 0.0; v[F_U_AG] += (ta || tg) ? 1.0 : 0.0;
+    v[F_I_BG] += (tb && tg) ? 1.0 : 0.0; v[F_U_BG] += (tb || tg) ? 1.0 : 0.0;
+    v[F_I_AB] += (ta && tb) ? 1.0 : 0.0; v[F_U_AB] += (ta || tb) ? 1.0 : 0.0;
+  }
+  int slot[F_NS1];
+#pragma unroll
+  for (int j = 0; j < F_NS1; j++) slot[j] = j;
+  block_add<F_NS1>(v, acc, slot);
+}
+
+// the two centroids: of gt >= 0.5 (pairs 1 and 2) and of b >= 0.5 (pair 3)
+DEV void flip_centroids(const double* acc, int H, int W, long& X, long& Y, long& XB, long& YB) {
+  double c[A_NSCAL];
+  c[A_N1] = acc[F_N1]; c[A_CX] = acc[F_CX]; c[A_CY] = acc[F_CY];
+  centroid(c, H, W, X, Y);
+  c[A_N1] = acc[F_NB1]; c[A_CX] = acc[F_BCX]; c[A_CY] = acc[F_BCY];
+  centroid(c, H, W, XB, YB);
+}
+
+__global__ void __launch_bounds__(TB) flip_region_kernel(const float* __restrict__ a, const float* __restrict__ bm,
+                                                         const float* __restrict__ gt, int H, int W, double* __restrict__ acc) {
+  long X, Y, XB, YB;
+  flip_centroids(acc, H, W, X, Y, XB, YB);
+  const long N = (long)H * W;
+  double v[FQ_N];
+#pragma unroll
+  for (int j = 0; j < FQ_N; j++) v[j] = 0.0;
+  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+    const long y = i / W, x = i - y * W;
+    const float pb = bm[i + (W - 1 - 2 * x)];
+    const double ad = a[i], bd = pb;
+    const double mg = gt[i] >= 0.5f ? 1.0 : 0.0, mb = pb >= 0.5f ? 1.0 : 0.0;
+    const int q = (y < Y ? 0 : 2) + (x < X ? 0 : 1);       // LT, RT, LB, RB
+    const int qb = (y < YB ? 0 : 2) + (x < XB ? 0 : 1);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      if (k == q) {
+        v[8 * k + 0] += 1.0; v[8 * k + 1] += mg;
+        v[8 * k + 2] += ad; v[8 * k + 3] += ad * ad; v[8 * k + 4] += ad * mg;
+        v[8 * k + 5] += bd; v[8 * k + 6] += bd * bd; v[8 * k + 7] += bd * mg;
+      }
+      if (k == qb) {
+        v[32 + 5 * k + 0] += 1.0; v[32 + 5 * k + 1] += mb;
+        v[32 + 5 * k + 2] += ad; v[32 + 5 * k + 3] += ad * ad; v[32 + 5 * k + 4] += ad * mb;
+      }
+    }
+  }
+  int slot[FQ_N];
+#pragma unroll
+  for (int j = 0; j < FQ_N; j++) slot[j] = FQ_G + j;
+  block_add<FQ_N>(v, acc, slot);
+}
+
+// S of one (pred, mask) pair from its sums, as final_kernel states it: ymean decides the special cases, q holds the
+// four quadrants' [n, sp, sm, spp, smm, spm]
+DEV double flip_s(double ymean, double xmean, double n1, double fg1, double fg2, double bg1, double bg2, long X, long Y,
+                  const double* q, int H, int W) {
+  if (ymean == 0.0) return 1.0 - xmean;
+  if (ymean == 1.0) return xmean;
+  const double Nd = (double)H * W, n0 = Nd - n1, u = n1 / Nd;
+  const double so = u * o_score(n1, fg1, fg2) + (1 - u) * o_score(n0, bg1, bg2);
+  const double w1 = (double)X * Y / Nd, w2 = (double)(W - X) * Y / Nd, w3 = (double)X * (H - Y) / Nd;
+  const double w4 = 1 - w1 - w2 - w3;
+  const double sr = w1 * q_ssim(q) + w2 * q_ssim(q + 6) + w3 * q_ssim(q + 12) + w4 * q_ssim(q + 18);
+  double S = 0.5 * so + 0.5 * sr;
+  if (S < 0) S = 0.0;
+  return S;
+}
+
+__global__ void flip_final_kernel(const double* __restrict__ acc, int H, int W, double* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  const double Nd = (double)H * W;
+  long X, Y, XB, YB;
+  flip_centroids(acc, H, W, X, Y, XB, YB);
+  double q1[24], q2[24], q3[24];
+  for (int k = 0; k < 4; k++) {
+    const double* g = acc + FQ_G + 8 * k;
+    const double* b = acc + FQ_B + 5 * k;
+    const double r1[6] = {g[0], g[2], g[1], g[3], g[1], g[4]};     // a vs g (g * g = g)
+    const double r2[6] = {g[0], g[5], g[1], g[6], g[1], g[7]};     // b vs g
+    const double r3[6] = {b[0], b[2], b[1], b[3], b[1], b[4]};     // a vs m
+    for (int j = 0; j < 6; j++) { q1[6 * k + j] = r1[j]; q2[6 * k + j] = r2[j]; q3[6 * k + j] = r3[j]; }
+  }
+  const double ysum = acc[F_YSUM], n1 = acc[F_N1], nb1 = acc[F_NB1];
+  // step 1 binarises gt in place unless its raw mean is 0 or 1 (region_kernel's `special`); step 2 then sees the
+  // binarised plane, whose mean is n1 / N
+  const bool special = ysum == 0.0 || ysum == Nd;
+  const double am = acc[F_ASUM] / Nd, bmean = acc[F_BSUM] / Nd;
+  out[0] = flip_s(ysum / Nd, am, n1, acc[F_AFG1], acc[F_AFG2], acc[F_ABG1], acc[F_ABG2], X, Y, q1, H, W);
+  out[1] = flip_s(special ? ysum / Nd : n1 / Nd, bmean, n1, acc[F_BFG1], acc[F_BFG2], acc[F_BBG1], acc[F_BBG2], X, Y, q2, H, W);
+  out[2] = flip_s(bmean, am, nb1, acc[F_CFG1], acc[F_CFG2], acc[F_CBG1], acc[F_CBG2], XB, YB, q3, H, W);
+  for (int j = 0; j < 6; j++) out[3 + j] = acc[F_I_AG + j];
+}
+
 }  // namespace
 
 extern "C" {
@@ -492,6 +635,37 @@ int s3od_eval_metrics(const float* pred, float* gt, int H, int W, const float* t
   hipLaunchKernelGGL(region_kernel, dim3(g), dim3(TB), 0, st, pred, gt, H, W, binarize, acc);
   hipLaunchKernelGGL(final_kernel, dim3(1), dim3(256), 0, st, (const double*)acc, H, W, sm_only, out);
   return s3od_check_launch("eval_metrics");
+}
+
+// *bytes (host) = scratch s3od_flip_scores needs for an H x W image (the accumulators; it does not grow with the image)
+int s3od_flip_scores_ws(int H, int W, long* bytes) {
+  S3OD_REQUIRE(bytes && H > 0 && W > 0, "flip_scores_ws: bad arguments");
+  *bytes = (long)F_WORDS * 8;
+  return 0;
+}
+
+// a: fp32 [H][W] soft mask of the image; bm: fp32 [H][W] soft mask of the mirrored image, still mirrored (read as
+// b(y, x) = bm[y][W-1-x]); gt: fp32 [H][W] in [0,1]; nothing is modified.  ws: device scratch of s3od_flip_scores_ws
+// bytes, 8-byte aligned; out: device double[9] = S(a, gt), S(b, gt'), S(a, b) as three EvaluationMetrics(sm_only)
+// steps in that order on the same tensors give them (gt' = gt binarised at 0.5 when step 1 did so, i.e. when gt's
+// raw mean is neither 0 nor 1), then intersection and union counts of (a, gt), (b, gt), (a, b) with a > threshold,
+// b > threshold, gt > 0.5.
+int s3od_flip_scores(const float* a, const float* bm, const float* gt, int H, int W, float threshold, void* ws, long ws_bytes,
+                     double* out, void* stream) {
+  S3OD_REQUIRE(a && bm && gt && ws && out, "flip_scores: null pointer");
+  S3OD_REQUIRE(H >= 2 && W >= 2 && H <= 32768 && W <= 32768, "flip_scores: image must be 2..32768 on each side");
+  S3OD_REQUIRE(ws_bytes >= (long)F_WORDS * 8 && (uintptr_t)ws % 8 == 0 && (uintptr_t)out % 8 == 0,
+               "flip_scores: workspace too small or workspace / output not 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const long N = (long)H * W;
+  double* acc = (double*)ws;
+  hipError_t e = hipMemsetAsync(acc, 0, (size_t)F_WORDS * 8, st);
+  if (e != hipSuccess) return (int)e;
+  const int g = sweep_grid(N);
+  hipLaunchKernelGGL(flip_stats_kernel, dim3(g), dim3(TB), 0, st, a, bm, gt, N, W, threshold, acc);
+  hipLaunchKernelGGL(flip_region_kernel, dim3(g), dim3(TB), 0, st, a, bm, gt, H, W, acc);
+  hipLaunchKernelGGL(flip_final_kernel, dim3(1), dim3(64), 0, st, (const double*)acc, H, W, out);
+  return s3od_check_launch("flip_scores");
 }
 
 }  // extern "C"

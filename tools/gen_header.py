@@ -55,6 +55,9 @@ REF = {
     "s3od_augment_ws_floats": "workspace size of s3od_augment_synthetic (new; albumentations allocates numpy temporaries)",
     "s3od_eval_metrics": "EvaluationMetrics.step (MAE, MaxF/AvgF, S-measure) + EMeasure + WeightedFMeasure on device: synth_sod/src/synth_sod/model_training/metrics.py:14-424",
     "s3od_eval_metrics_ws": "scratch size of s3od_eval_metrics (new; the reference allocates numpy temporaries)",
+    "s3od_flip_scores": "eval_sample's three sm_only EvaluationMetrics steps (image, un-mirrored flip, consistency) + the consistency filter's three binary IoUs in one pass: synth_sod/src/synth_sod/model_training/mine_samples.py:16-51, synth_sod/src/synth_sod/data_generation/filters/consistency_filter.py:49-95",
+    "s3od_flip_scores_ws": "scratch size of s3od_flip_scores (new; the reference allocates torch temporaries)",
+    "s3od_mirror_u8": "cv2.flip(image, 1) of the uint8 source image on device: synth_sod/src/synth_sod/model_training/mine_samples.py:26, consistency_filter.py:69",
     "s3od_preprocess": "BackgroundRemoval._preprocess normalisation: src/s3od/predictor.py:79-94",
     "s3od_preprocess_batch": "BackgroundRemoval._preprocess over a list of differently sized images, one launch (S3odPreDesc table): src/s3od/predictor.py:79-94",
     "s3od_best_index": "sigmoid(pred_iou) + argmax per image on device: src/s3od/predictor.py:113-116, 125",
