@@ -9,6 +9,11 @@ download stream, and one event.  Chunk k+1 is staged and uploaded while chunk k 
 and split on the host while chunk k+1 computes (two slots of every buffer; events order their reuse).  Every call
 takes this one path and gets one ``ImageOutputs`` per image; what a ``Request`` leaves out is ``None`` there and
 never leaves the device.  The arrays handed back are copies: they own their memory.
+
+With ``Request.refine`` (``matte.Refine``) the post-processing kernels write no RGBA or composite (their rows are
+MODE_NONE) and leave the best float plane on the device; ``_refine`` then runs s3od_matte_refine, s3od_matte_foreground
+and s3od_compose per image on the compute stream, into the same packed outputs at the planned offsets, before the
+slot's ``done`` event: the upload and download overlap is that of the unrefined path.
 """
 from __future__ import annotations
 
@@ -24,6 +29,7 @@ from PIL import Image
 from .image_ops import (MODE_MASK_U8, MODE_NONE, MODE_RGB_OVER_COLOR, MODE_RGB_OVER_IMAGE, MODE_RGBA,  # noqa: F401
                         STATS_WORDS, OutDesc, PostDesc, PreDesc, normalize_background, normalize_backgrounds, pack_color,
                         reference_geometry)                     # the unused ones stay importable from here
+from .matte import Refine
 
 
 def classify_geometry(h: int, w: int, image_size: int, exact_reference_quirks: bool = True, index: Optional[int] = None) -> str:
@@ -48,6 +54,7 @@ class Request:
     backgrounds: Optional[Sequence] = None      # per image a ``normalize_background`` value: the composite over it
     want_stats: bool = False
     threshold: float = 0.5          # of the statistics' area and bounding box
+    refine: Optional[Refine] = None     # the best mask is refined (and the foreground estimated) before the outputs are written
 
 
 class ImageOutputs(NamedTuple):
@@ -58,18 +65,23 @@ class ImageOutputs(NamedTuple):
     rgba: Optional[np.ndarray]              # uint8 [H0, W0, 4]
     composite: Optional[Image.Image]        # RGB
     stats_words: Optional[np.ndarray]       # uint32 [STATS_WORDS]
+    refined: Optional[np.ndarray] = None    # fp32 [H0, W0]: the refined best mask (``Request.refine`` with masks wanted)
 
 
 @dataclass
 class ChunkPlan:
     """Byte layout of one chunk.  Input offsets are bytes into the staging buffer; ``ious_off`` .. ``stats_off`` are
     bytes into the packed outputs, the descriptors' ``mask_off`` / ``tmp_off`` / ``scratch_off`` count floats from
-    ``masks_off`` / the tmp / the scratch buffer and ``out_off`` / ``stats_off`` bytes from ``outs_off`` / ``stats_off``."""
+    ``masks_off`` / the tmp / the scratch buffer and ``out_off`` / ``stats_off`` bytes from ``outs_off`` / ``stats_off``.
+    ``rows`` holds what each image's output rows contain; ``outd`` is what the post-processing kernels are told to
+    write, which is nothing (MODE_NONE) under ``refine``.  ``out_bytes`` of the packed outputs come back to the host;
+    the buffer has ``dev_bytes``, and what lies beyond ``out_bytes`` stays on the device."""
     shapes: List[tuple]
     pre: Any                    # (PreDesc * B) at pre_off
     post: Any                   # (PostDesc * B) at post_off
     outd: Any                   # (OutDesc * (B * n_out)) at out_desc_off
     n_out: int
+    rows: List[list]            # per image (mode, out_off, color, bg_off) of every row that is written
     pre_off: int
     post_off: int
     out_desc_off: int
@@ -86,6 +98,10 @@ class ChunkPlan:
     out_bytes: int
     tmp_bytes: int
     scratch_bytes: int          # 0 unless the statistics need planes that are not kept
+    dev_planes: int = 0         # float planes the kernels store per image: ``planes``, or 1 when only ``refine`` needs one
+    dev_bytes: int = 0
+    refine: Optional[Refine] = None
+    ref_off: Optional[List[int]] = None     # per image the byte offset of the refined plane in the packed outputs
 
 
 def plan_chunk(shapes: Sequence[tuple], geoms: Sequence[tuple], NM: int, LH: int, LW: int, req: Request) -> ChunkPlan:
@@ -102,10 +118,11 @@ def plan_chunk(shapes: Sequence[tuple], geoms: Sequence[tuple], NM: int, LH: int
     pre, post, outd = (PreDesc * B)(), (PostDesc * B)(), (OutDesc * (B * n_out))()
     all_masks = req.all_masks and req.want_masks
     planes = (NM if all_masks else 1) if req.want_masks else 0
+    dev_planes = max(planes, 1) if req.refine is not None else planes
     lplanes = NM if (all_masks or req.want_stats) else 1            # planes the kernels resample
     use_scratch = req.want_stats and not all_masks
     mask_floats = out_bytes = tmp_floats = scratch_floats = 0
-    bg_copies = []
+    bg_copies, rows = [], []
     for b, ((H0, W0), g, bg) in enumerate(zip(shapes, geoms, bgs)):
         nh, nw, top, left, ph, pw = g
         pre[b] = PreDesc(off, H0, W0, nh, nw, top, left)
@@ -122,32 +139,49 @@ def plan_chunk(shapes: Sequence[tuple], geoms: Sequence[tuple], NM: int, LH: int
             bg_off = off
             bg_copies.append((off, bg))
             off = _align(off + H0 * W0 * 3)
+        rows.append([])
         for k, mode in enumerate(modes + [MODE_NONE] * (n_out - len(modes))):
             outd[b * n_out + k] = OutDesc(bg_off if mode == MODE_RGB_OVER_IMAGE else 0, out_bytes,
-                                          b * STATS_WORDS * 4 if req.want_stats else -1, scratch_floats, mode,
+                                          b * STATS_WORDS * 4 if req.want_stats else -1, scratch_floats,
+                                          mode if req.refine is None else MODE_NONE,
                                           color if mode == MODE_RGB_OVER_COLOR else 0)
+            if mode != MODE_NONE:
+                rows[b].append((mode, out_bytes, color, bg_off))
             out_bytes = _align(out_bytes + H0 * W0 * (4, 3, 3, 1, 0)[mode])
-        mask_floats += planes * H0 * W0
+        mask_floats += dev_planes * H0 * W0
         tmp_floats += lplanes * h * W0
         scratch_floats += NM * H0 * W0 if use_scratch else 0
+    # packed outputs: IoUs | best | float planes | refined planes (beside every plane) | rows | counters, then what
+    # stays on the device: the one plane per image that only the refinement reads
     ious_off = 0
     best_off = ious_off + B * NM * 4
     masks_off = _align(best_off + B * 4)
-    outs_off = _align(masks_off + mask_floats * 4)
+    ref_floats = sum(H0 * W0 for H0, W0 in shapes) if req.refine is not None and all_masks else 0
+    refs_off = _align(masks_off + (mask_floats * 4 if planes else 0))
+    outs_off = _align(refs_off + ref_floats * 4)
     stats_off = _align(outs_off + out_bytes)
-    return ChunkPlan(shapes=[tuple(s) for s in shapes], pre=pre, post=post, outd=outd, n_out=n_out, pre_off=pre_off,
+    end = stats_off + (B * STATS_WORDS * 4 if req.want_stats else 0)
+    if dev_planes and not planes:
+        masks_off = _align(end)
+    ref_off = None
+    if req.refine is not None:          # with one plane per image the refinement is in place; otherwise beside the planes
+        ref_off = [masks_off + d.mask_off * 4 for d in post]
+        if all_masks:
+            ref_off = [refs_off + 4 * sum(h * w for h, w in shapes[:b]) for b in range(B)]
+    return ChunkPlan(shapes=[tuple(s) for s in shapes], pre=pre, post=post, outd=outd, n_out=n_out, rows=rows, pre_off=pre_off,
                      post_off=post_off, out_desc_off=out_desc_off, bg_copies=bg_copies, in_bytes=off, all_masks=all_masks,
                      planes=planes, threshold=float(req.threshold), ious_off=ious_off, best_off=best_off,
                      masks_off=masks_off, outs_off=outs_off, stats_off=stats_off if req.want_stats else None,
-                     out_bytes=stats_off + (B * STATS_WORDS * 4 if req.want_stats else 0),
-                     tmp_bytes=max(tmp_floats * 4, 16), scratch_bytes=max(scratch_floats * 4, 16) if use_scratch else 0)
+                     out_bytes=end, tmp_bytes=max(tmp_floats * 4, 16),
+                     scratch_bytes=max(scratch_floats * 4, 16) if use_scratch else 0, dev_planes=dev_planes,
+                     dev_bytes=max(end, masks_off + mask_floats * 4 if dev_planes else 0), refine=req.refine, ref_off=ref_off)
 
 
 class _Slot:
     """One set of staging buffers and the events that order their reuse."""
 
     def __init__(self):
-        self.pin_in = self.dev_in = self.dev_out = self.pin_out = self.tmp = self.scratch = None
+        self.pin_in = self.dev_in = self.dev_out = self.pin_out = self.tmp = self.scratch = self.fg = None
         self.h2d = torch.cuda.Event()      # upload of this slot finished (copy stream)
         self.done = torch.cuda.Event()     # kernels that read dev_in finished (compute stream)
         self.out = torch.cuda.Event()      # download into pin_out finished (download stream)
@@ -214,7 +248,7 @@ class BatchEngine:
         main = torch.cuda.current_stream()
         main.wait_event(slot.h2d)
         dev_in, pin_in = slot.dev_in, slot.pin_in
-        dev_out = self._ensure(slot, "dev_out", plan.out_bytes, False)
+        dev_out = self._ensure(slot, "dev_out", plan.dev_bytes, False)
         pin_out = self._ensure(slot, "pin_out", plan.out_bytes, True)
         tmp = self._ensure(slot, "tmp", plan.tmp_bytes, False)
         scratch = self._ensure(slot, "scratch", plan.scratch_bytes, False) if plan.scratch_bytes else None
@@ -231,8 +265,10 @@ class BatchEngine:
         lib()("s3od_postprocess_batch_out", logits, B, NM, LH, LW, o + plan.best_off, dev_in,
               dev_in.data_ptr() + plan.post_off, pin_in.data_ptr() + plan.post_off,
               dev_in.data_ptr() + plan.out_desc_off, pin_in.data_ptr() + plan.out_desc_off, plan.n_out,
-              1 if plan.all_masks else 0, (o + plan.masks_off) if plan.planes else None, o + plan.outs_off, tmp,
+              1 if plan.all_masks else 0, (o + plan.masks_off) if plan.dev_planes else None, o + plan.outs_off, tmp,
               scratch, None if plan.stats_off is None else o + plan.stats_off, plan.threshold, stream())
+        if plan.refine is not None:
+            self._refine(slot, NM)
         slot.done.record(main)
         with torch.cuda.stream(self.out_stream):        # the download overlaps the next chunk's kernels
             self.out_stream.wait_event(slot.done)
@@ -240,6 +276,31 @@ class BatchEngine:
             slot.out.record(self.out_stream)
         slot.out_plan = plan
         slot.used = True                                # x / logits live on the compute stream only: the allocator orders them
+
+    def _refine(self, slot: _Slot, NM):
+        """Per image of the slot's chunk: the best plane (gathered by the device's best index when every plane is
+        kept) is refined in place at ``ref_off``, the foreground is estimated into the slot's colour buffer, and
+        s3od_compose writes the image's rows from them.  Everything is enqueued on the compute stream."""
+        from .compose import compose
+        from .matte import estimate_foreground, refine_alpha
+        plan, rf, dev_in, dev_out = slot.plan, slot.plan.refine, slot.dev_in, slot.dev_out
+        best = dev_out[plan.best_off:plan.best_off + 4 * len(plan.shapes)].view(torch.int32)
+        if rf.foreground:
+            fg = self._ensure(slot, "fg", max(H0 * W0 for H0, W0 in plan.shapes) * 3, False)
+        for b, (H0, W0) in enumerate(plan.shapes):
+            n = H0 * W0
+            m = dev_out[plan.ref_off[b]:plan.ref_off[b] + 4 * n].view(torch.float32).view(H0, W0)
+            if plan.all_masks:
+                m0 = plan.masks_off + plan.post[b].mask_off * 4
+                torch.index_select(dev_out[m0:m0 + 4 * NM * n].view(torch.float32).view(NM, n), 0, best[b:b + 1],
+                                   out=m.view(1, n))
+            src = dev_in[plan.pre[b].img_off:plan.pre[b].img_off + 3 * n].view(H0, W0, 3)
+            refine_alpha(m, src, rf.radius, rf.eps, out=m)
+            if rf.foreground:
+                src = estimate_foreground(m, src, rf.fg_radius, out=fg[:3 * n].view(H0, W0, 3))
+            for mode, out_off, color, bg_off in plan.rows[b]:
+                compose(m, src, mode, color, dev_in[bg_off:bg_off + 3 * n].view(H0, W0, 3) if mode == MODE_RGB_OVER_IMAGE else None,
+                        out=dev_out, out_offset=plan.outs_off + out_off, pitch=W0 * (4, 3, 3, 1)[mode])
 
     def _collect(self, slot: _Slot, NM) -> List[ImageOutputs]:
         self._timed("wait", slot.out.synchronize)
@@ -252,22 +313,25 @@ class BatchEngine:
         best = host[plan.best_off:plan.best_off + B * 4].view(np.int32).copy()
         res = []
         for b, (H0, W0) in enumerate(plan.shapes):
-            masks = rgba = comp = words = None
+            masks = rgba = comp = words = refined = None
             if planes:
                 m0 = plan.masks_off + plan.post[b].mask_off * 4
                 masks = host[m0:m0 + planes * H0 * W0 * 4].view(np.float32).reshape(planes, H0, W0).copy()
-            for o in plan.outd[b * plan.n_out:(b + 1) * plan.n_out]:
-                r0 = plan.outs_off + o.out_off
-                if o.mode == MODE_RGBA:
+            if planes and plan.ref_off is not None:
+                refined = masks[0] if not plan.all_masks else \
+                    host[plan.ref_off[b]:plan.ref_off[b] + H0 * W0 * 4].view(np.float32).reshape(H0, W0).copy()
+            for mode, out_off, _, _ in plan.rows[b]:
+                r0 = plan.outs_off + out_off
+                if mode == MODE_RGBA:
                     rgba = host[r0:r0 + H0 * W0 * 4].reshape(H0, W0, 4).copy()
-                elif o.mode != MODE_NONE:
+                else:
                     # PIL keeps RGB as 4 bytes per pixel, so this unpacks into memory the image owns: the one
                     # copy out of the pinned buffer, made here while the next chunk computes
                     comp = Image.frombuffer("RGB", (W0, H0), host[r0:r0 + H0 * W0 * 3], "raw", "RGB", 0, 1)
             if plan.stats_off is not None:
                 s0 = plan.stats_off + b * STATS_WORDS * 4
                 words = host[s0:s0 + STATS_WORDS * 4].view(np.uint32).copy()
-            res.append(ImageOutputs(ious[b], int(best[b]), masks, rgba, comp, words))
+            res.append(ImageOutputs(ious[b], int(best[b]), masks, rgba, comp, words, refined))
         return res
 
     # ------------------------------------------------------------------ the list

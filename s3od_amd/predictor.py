@@ -15,7 +15,10 @@ list go through it (``_remove_background``) because they cannot share the S x S 
 Both take ``background=`` (an (r, g, b) colour or an image of the source's size) and ``stats=True``: the subject
 composited over the background (``RemovalResult.composite``, the reference visualizer's blend) and the pairwise
 mask IoU counts, area and bounding box (``RemovalResult.stats``, a ``MaskStats``) are produced on the device, so
-3 B/px and a 288-byte counter block come back in place of float masks (``compose.py``).
+3 B/px and a 288-byte counter block come back in place of float masks (``compose.py``).  ``refine=Refine(...)``
+(``matte.py``) guided-filters the best mask against the full-size image and estimates the foreground colours, on the
+device: ``predicted_mask``, the alpha and the colours of ``rgba_image`` and ``composite`` are the refined ones, while
+``all_masks``, ``all_ious`` and ``stats`` stay as the model produced them.  ``refine=None`` changes nothing.
 
 Model loading is offline-safe: a local checkpoint path is tried first (``torch.load`` with
 ``weights_only=True``; ``{"state_dict": ...}``, Lightning ``model.``-prefixed and both
@@ -43,6 +46,7 @@ from PIL import Image
 from .utils import get_pad_info, remove_padding  # noqa: F401  (re-exported like the reference)
 from .model import DPTSegmentation
 from .compose import MAX_STAT_MASKS, MaskStats, compose, mask_stats_words
+from .matte import Refine, estimate_foreground, refine_alpha
 from .image_ops import (MODE_RGB_OVER_COLOR, MODE_RGB_OVER_IMAGE, normalize_background, normalize_backgrounds,
                         preprocess_single, reference_geometry, run_single)
 from .infer_many import BatchEngine, Request
@@ -115,33 +119,44 @@ class BackgroundRemoval:
 
     @torch.no_grad()
     def remove_background(self, image: Union[np.ndarray, Image.Image], threshold: float = 0.5, *, background=None,
-                          stats: bool = False) -> RemovalResult:
+                          stats: bool = False, refine: Optional[Refine] = None) -> RemovalResult:
         """``background``: None, an (r, g, b) tuple or a uint8 array / PIL image of the image's size (any other size
         raises ``ValueError``; backgrounds are not resized) -> ``result.composite``, the subject over it as a PIL RGB
         image.  ``stats=True`` -> ``result.stats`` (``MaskStats``); ``threshold`` sets its ``area`` and ``bbox`` and
-        nothing else.  Both run on the device masks (s3od_compose, s3od_mask_stats)."""
+        nothing else.  Both run on the device masks (s3od_compose, s3od_mask_stats).  ``refine``: a ``Refine``; the
+        best mask is refined against the image (s3od_matte_refine) and, with ``Refine.foreground``, the colours of
+        ``rgba_image`` and ``composite`` are the estimated foreground (s3od_matte_foreground)."""
         if isinstance(image, Image.Image):
             image = np.array(image.convert("RGB"))
-        return self._remove_background(image, threshold, normalize_background(background, image.shape[:2]), stats)
+        return self._remove_background(image, threshold, normalize_background(background, image.shape[:2]), stats, refine)
 
-    def _remove_background(self, image: np.ndarray, threshold: float, bg, stats: bool) -> RemovalResult:
+    def _remove_background(self, image: np.ndarray, threshold: float, bg, stats: bool,
+                           refine: Optional[Refine] = None) -> RemovalResult:
         """``remove_background`` of an array with the background already normalised (``normalize_background``)."""
         if image.dtype != np.uint8:
             raise TypeError(f"an image array is uint8, got {image.dtype}")
+        if refine is not None and not isinstance(refine, Refine):
+            raise TypeError(f"refine is None or a Refine, got {refine!r}")
         geom, quirk2 = self._geometry(*image.shape[:2])
         masks, iou_logits, img_dev = run_single(self.model, image, geom, self.image_size, self.device, unpadded=quirk2)
         pred_ious = torch.sigmoid(iou_logits).cpu().numpy()   # 3 floats
         all_masks = masks.cpu().numpy()
         best_idx = pred_ious.argmax()
-        predicted_mask = all_masks[best_idx]
+        predicted_mask, best_dev, colors, colors_dev = all_masks[best_idx], masks[best_idx], image, img_dev
+        if refine is not None:                  # the planes of all_masks and the statistics stay the model's
+            best_dev = refine_alpha(best_dev, img_dev, refine.radius, refine.eps)
+            predicted_mask = best_dev.cpu().numpy()
+            if refine.foreground:
+                colors_dev = estimate_foreground(best_dev, img_dev, refine.fg_radius)
+                colors = colors_dev.cpu().numpy()
         alpha = (predicted_mask * 255).astype(np.uint8)
-        rgba = np.dstack([image, alpha])
+        rgba = np.dstack([colors, alpha])
         composite = mask_stats = None
         if bg is not None:
             if isinstance(bg, int):
-                comp = compose(masks[best_idx], img_dev, MODE_RGB_OVER_COLOR, bg)
+                comp = compose(best_dev, colors_dev, MODE_RGB_OVER_COLOR, bg)
             else:
-                comp = compose(masks[best_idx], img_dev, MODE_RGB_OVER_IMAGE, 0, torch.from_numpy(bg).to(self.device))
+                comp = compose(best_dev, colors_dev, MODE_RGB_OVER_IMAGE, 0, torch.from_numpy(bg).to(self.device))
             composite = Image.fromarray(comp.cpu().numpy())
         if stats:
             if len(masks) > MAX_STAT_MASKS:
@@ -154,7 +169,8 @@ class BackgroundRemoval:
     @torch.no_grad()
     def remove_background_many(self, images: Sequence[Union[np.ndarray, Image.Image]], threshold: float = 0.5,
                                batch_size: int = 8, return_all_masks: bool = True, background=None, stats: bool = False,
-                               return_masks: bool = True, return_rgba: bool = True) -> List[RemovalResult]:
+                               return_masks: bool = True, return_rgba: bool = True, *,
+                               refine: Optional[Refine] = None) -> List[RemovalResult]:
         """``remove_background`` over a list of differently sized images, ``batch_size`` per forward
         (s3od_preprocess_batch / s3od_postprocess_batch_out, see ``infer_many.BatchEngine``).  Results come back
         in input order.  ``return_all_masks=False`` leaves ``all_masks`` None and brings only the best mask
@@ -167,7 +183,13 @@ class BackgroundRemoval:
         where they write RGBA, the background images ride in the same staging buffer and upload as the sources,
         and the counters come from the device masks.  ``return_masks=False`` leaves ``predicted_mask`` and
         ``all_masks`` None (no float plane leaves the device) and ``return_rgba=False`` leaves ``rgba_image``
-        None; asking for nothing at all raises ``ValueError``."""
+        None; asking for nothing at all raises ``ValueError``.
+
+        ``refine`` is that of ``remove_background`` and gives the same bytes: the best float plane stays on the device,
+        the refinement, the foreground estimate and s3od_compose run per image on the compute stream and write into
+        the packed outputs, so upload, compute and download overlap as without it."""
+        if refine is not None and not isinstance(refine, Refine):
+            raise TypeError(f"refine is None or a Refine, got {refine!r}")
         if batch_size < 1:
             raise ValueError(f"batch_size must be >= 1, got {batch_size}")
         if not (return_masks or return_rgba or stats or background is not None):
@@ -187,10 +209,12 @@ class BackgroundRemoval:
         outs = self._many.run([np.ascontiguousarray(arrays[i], dtype=np.uint8) for i in batched],
                               [geoms[i][0] for i in batched], batch_size, NM,
                               Request(all_masks=return_all_masks, want_masks=return_masks, want_rgba=return_rgba,
-                                      backgrounds=[bgs[i] for i in batched], want_stats=stats, threshold=threshold))
+                                      backgrounds=[bgs[i] for i in batched], want_stats=stats, threshold=threshold,
+                                      refine=refine))
         for i, o in zip(batched, outs):     # the images wrap the arrays they own: no second copy
             results[i] = RemovalResult(
-                predicted_mask=None if o.masks is None else o.masks[o.best if return_all_masks else 0],
+                predicted_mask=o.refined if refine is not None else
+                None if o.masks is None else o.masks[o.best if return_all_masks else 0],
                 all_masks=o.masks if return_all_masks else None, all_ious=o.ious,
                 rgba_image=None if o.rgba is None else
                 Image.frombuffer("RGBA", (o.rgba.shape[1], o.rgba.shape[0]), o.rgba, "raw", "RGBA", 0, 1),
@@ -198,7 +222,7 @@ class BackgroundRemoval:
                 stats=None if o.stats_words is None else MaskStats.from_words(o.stats_words, NM))
         for i, (_, quirk2) in enumerate(geoms):
             if quirk2:                      # the single-image path, trimmed to what was asked for
-                r = results[i] = self._remove_background(arrays[i], threshold, bgs[i], stats)
+                r = results[i] = self._remove_background(arrays[i], threshold, bgs[i], stats, refine)
                 if not return_rgba:
                     r.rgba_image = None
                 if not (return_masks and return_all_masks):

@@ -65,6 +65,9 @@ REF = {
     "s3od_postprocess_batch_out": "s3od_postprocess_batch with per-image outputs (S3odOutDesc table): RGBA, the visualizer's blend over a colour or an image, the mask as uint8, and the demo's pairwise mask IoU counts: src/s3od/visualizer.py:17-21, demo/app.py:38-56, 98",
     "s3od_compose": "visualize_removal / visualize_all_masks blend of a finished mask, RGBA and 8-bit mask outputs: src/s3od/visualizer.py:17-21, 45-46, src/s3od/predictor.py:127-130, demo/app.py:98",
     "s3od_mask_stats": "compute_mask_iou counts for every pair of masks (the demo's ambiguity flag) + area and bounding box of the best mask: demo/app.py:38-56",
+    "s3od_matte_ws": "scratch size of s3od_matte_refine and s3od_matte_foreground for an H x W image (new; the reference has neither)",
+    "s3od_matte_refine": "image-guided refinement of the resampled mask, the colour guided filter (He, Sun, Tang 2013), q = clip(box(a) . I + box(b), 0, 1) with I = src / 255 and clipped-window means (new; the reference returns the resampled mask of src/s3od/predictor.py:118-126 as it is). mask: fp32 [H][W]; src: uint8 [H][W][3], any byte alignment; out: fp32 [H][W], may alias mask; 1 <= r <= 256 (a window larger than the image is the image), 1e-6 <= eps <= 1; 2 <= H, W <= 32768. Float64 sums and solve, no atomics: the same inputs give the same bits",
+    "s3od_matte_foreground": "foreground colours under the alpha, the one-pass blur-fusion estimate (Forte & Pitie 2021), F = clip(F^ + a (I - a F^ - (1 - a) B^), 0, 1) as (unsigned char)(F * 255 + 0.5) (new; the reference composes the source pixel's own colour, src/s3od/predictor.py:127-130, src/s3od/visualizer.py:17-21). alpha: fp32 [H][W]; src: uint8 [H][W][3]; out_rgb: uint8 [H][W][3], not src; 1 <= r <= 256; 2 <= H, W <= 32768",
     "s3od_linear_wgrad_ws": "workspace query of s3od_linear_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_conv_wgrad_ws": "workspace query of s3od_conv_wgrad: bytes of the caller-owned split-K slab (new; PyTorch autograd allocates internally)",
     "s3od_token_prefix_bwd": "cat([cls, register_tokens, patches]) backward: tf:modeling_dinov3_vit.py:88-92 (reference: implicit torch autograd)",
@@ -88,6 +91,8 @@ WS = {
     "s3od_colsum": "ws (nullable): >= s3od_colsum_ws bytes of fp32 partial sums, contents dead between calls (with it the sum is two fixed-order passes: deterministic, no same-address atomics; without it one fp32 atomic per column per block)",
     "s3od_mask_stats": "stats: 72 uint32 words (288 bytes), contents dead on entry: the entry initialises them on the stream. [k] = #(m_i > 0.5 && m_j > 0.5) and [28 + k] = #(m_i > 0.5 || m_j > 0.5) for the pair i < j at k = i (15 - i) / 2 + j - i - 1; [56 + c] = #(m_c > 0.5); [64] = #(m_best > threshold); [65..68] = x0, y0, x1, y1 of those pixels' bounding box (x1, y1 exclusive; without meaning when [64] is 0); [69..71] unused",
     "s3od_postprocess_batch_out": "stats (nullable): one 288-byte block of 72 uint32 per image at stats_off, initialised on the stream; scratch (nullable): fp32 [NM][H0][W0] per image at scratch_off, needed with stats unless all_masks != 0 and masks is given, contents dead between calls",
+    "s3od_matte_refine": "ws: >= s3od_matte_ws bytes, 4-byte aligned, contents dead between calls (17 fp32 [H][W] planes: 13 window moments, 4 coefficients)",
+    "s3od_matte_foreground": "ws: >= s3od_matte_ws bytes, 4-byte aligned, contents dead between calls (7 fp32 [H][W] planes are used)",
     "s3od_linear_wgrad": "slab (nullable): >= s3od_linear_wgrad_ws bytes, contents dead between calls (without it the split-K partials are fp32 atomics into dw)",
 }
 
