@@ -8,15 +8,17 @@
 // LDS reductions and one global (vector) atomic per block and accumulator; the only serial work is
 // the distance transform's 1D lower envelopes (one thread per column / per row).
 //
-// Pass order on `stream`:
+// Pass order on `stream` (sm_only runs stats, region, final):
 //   stats   : MAE, sum gt, binarised-mask moments (S_object), centroid moments, PR histogram
-//             (bin = last threshold <= p), uint8 E-measure histograms, EDT-free
-//   region  : centroid -> quadrant moments (S_region); optional in-place binarisation of gt
+//             (bin = last threshold <= p), uint8 E-measure histograms
 //   edt_col : nearest foreground row per column (ties -> lower row)
 //   edt_row : Maurer lower envelope per row (strict remove / strict advance: ties -> lower column),
 //             which reproduces scipy.ndimage.distance_transform_edt(return_indices=True)'s choice
 //   wf_et   : E = |p - g|, Et = E at the nearest foreground pixel
 //   wf_sum  : EA = f32(7x7 Gaussian of Et, zero border), Ew sums
+//   region  : centroid -> quadrant moments (S_region); optional in-place binarisation of gt.  It is the only pass
+//             that writes gt, so it runs after the distance transform and the weighted-F passes: every reader
+//             sees gt as the caller gave it (their foreground, gt >= 0.5, is the same before and after)
 //   final   : one block: E-measure curve, F curve, S-measure, weighted F -> out[6]
 #include "common.hpp"
 
@@ -26,7 +28,8 @@ constexpr int NT = 255;          // PR thresholds (metrics.py:251)
 constexpr int TB = 256;          // threads per block for the sweeps
 constexpr double EPS = 2.220446049250313e-16;   // np.spacing(1)
 
-// accumulator slots (double) at the start of the workspace
+// accumulator slots (double) at the start of the workspace; a kernel's partial sums are indexed by these names and go
+// out as one consecutive run (block_add): A_MAE .. A_PSUM from stats_kernel, A_EWFG, A_EWBG from wf_sum_kernel
 enum {
   A_MAE = 0, A_YSUM, A_N1, A_FG1, A_FG2, A_BG1, A_BG2, A_CX, A_CY, A_PSUM,
   A_EWFG, A_EWBG, A_NSCAL
@@ -44,9 +47,13 @@ struct Tables {
   double k7[49];     // matlab_style_gauss2D((7,7), 5)
 };
 
-// block-wide sum of NV doubles, thread 0 adds them to dst[slot[i]]
+// one grid-stride sweep over N pixels by blocks of TB threads
+#define SWEEP(i, N) for (long i = blockIdx.x * (long)TB + threadIdx.x; i < (N); i += (long)gridDim.x * TB)
+
+// block-wide sums of NV doubles; thread i < NV adds sum i to acc[i]
 template <int NV>
-DEV void block_add(double (&v)[NV], double* acc, const int (&slot)[NV]) {
+DEV void block_add(const double (&v)[NV], double* acc) {
+  static_assert(NV <= TB, "one thread of the block per accumulator");
   __shared__ double red[TB / 64][NV];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -58,11 +65,28 @@ DEV void block_add(double (&v)[NV], double* acc, const int (&slot)[NV]) {
   if (threadIdx.x < NV) {
     double s = 0.0;
     for (int j = 0; j < TB / 64; j++) s += red[j][threadIdx.x];
-    // NV <= 64: one lane per accumulator
-    int i = threadIdx.x;
-    atomicAdd(acc + slot[i], s);
+    atomicAdd(acc + threadIdx.x, s);
   }
 }
+
+// The per-pixel updates below pick their accumulators by a condition.  That branch is a macro, so that it stays in
+// the kernel: as part of a function the compiler turns it into one update at a computed index before it inlines
+// it, and the kernel's partial sums, which must be registers, land in private memory.
+DEV void mom_add(double* o, double x) { o[0] += x; o[1] += x * x; }
+template <int K>
+DEV void terms_add(double* v, const double (&t)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; j++) v[j] += t[j];
+}
+
+// S_object moments of one pixel: o[0..3] = sum p, p^2 on the mask, sum q, q^2 off it; q = 1 - p is taken in float32,
+// as the reference does
+#define OBJ_ADD(o, on, p) \
+  do { if (on) mom_add(o, (double)(p)); else mom_add((o) + 2, (double)(1.f - (p))); } while (0)
+
+// adds the terms t[K] of one pixel to the moments of its quadrant q in v[4][K]
+#define QUAD_ADD(v, q, t) \
+  _Pragma("unroll") for (int k = 0; k < 4; k++) if (k == (q)) terms_add((v) + (int)std::size(t) * k, t)
 
 DEV int pr_bin(const float* thr, float p) {     // largest i with thr[i] <= p, -1 if none
   int lo = 0, hi = NT;                            // invariant: thr[<lo] <= p, thr[>=hi] > p
@@ -82,20 +106,18 @@ __global__ void __launch_bounds__(TB) stats_kernel(const float* __restrict__ pre
   hc[threadIdx.x] = hf[threadIdx.x] = hb[threadIdx.x] = 0ull;
   ht[threadIdx.x] = 0.0;
   __syncthreads();
-  double v[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+  double v[A_PSUM + 1] = {};                     // A_MAE .. A_PSUM
+  SWEEP(i, N) {
     const float p = pred[i], m = gt[i];
     const double pd = p, md = m;
-    v[0] += fabs(pd - md);                       // |pred - mask| in float64 (pred f32, mask f64)
-    v[1] += md;
-    v[9] += pd;
+    v[A_MAE] += fabs(pd - md);                   // |pred - mask| in float64 (pred f32, mask f64)
+    v[A_YSUM] += md;
+    v[A_PSUM] += pd;
     if (m >= 0.5f) {                             // binarised mask (metrics.py:239-240)
       const long y = i / W, x = i - y * W;
-      v[2] += 1.0; v[3] += pd; v[4] += pd * pd; v[7] += (double)x; v[8] += (double)y;
-    } else {                                     // bg = 1 - pred (float32 in the reference)
-      const double q = (double)(1.f - p);
-      v[5] += q; v[6] += q * q;
+      v[A_N1] += 1.0; v[A_CX] += (double)x; v[A_CY] += (double)y;
     }
+    OBJ_ADD(v + A_FG1, m >= 0.5f, p);
     if (!sm_only) {
       const int b = pr_bin(thr, p);
       if (b >= 0) {
@@ -108,8 +130,7 @@ __global__ void __launch_bounds__(TB) stats_kernel(const float* __restrict__ pre
       if (m >= 0.5f) atomicAdd(&hf[u], 1ull); else atomicAdd(&hb[u], 1ull);
     }
   }
-  const int slot[10] = {A_MAE, A_YSUM, A_N1, A_FG1, A_FG2, A_BG1, A_BG2, A_CX, A_CY, A_PSUM};
-  block_add<10>(v, acc, slot);
+  block_add(v, acc + A_MAE);
   if (!sm_only) {
     __syncthreads();
     const int t = threadIdx.x;
@@ -122,43 +143,33 @@ __global__ void __launch_bounds__(TB) stats_kernel(const float* __restrict__ pre
 }
 
 // centroid (metrics.py:358-378): round-half-even of the exact mean coordinate; empty mask -> round(dim/2)
-DEV void centroid(const double* acc, int H, int W, long& X, long& Y) {
-  const double n1 = acc[A_N1];
+DEV void centroid(double n1, double cx, double cy, int H, int W, long& X, long& Y) {
   if (n1 == 0.0) {
     X = (long)rint(W / 2.0); Y = (long)rint(H / 2.0);
   } else {
-    X = (long)rint(acc[A_CX] / n1); Y = (long)rint(acc[A_CY] / n1);
+    X = (long)rint(cx / n1); Y = (long)rint(cy / n1);
   }
 }
+
+DEV int quadrant(long x, long y, long X, long Y) { return (y < Y ? 0 : 2) + (x < X ? 0 : 1); }   // LT, RT, LB, RB
 
 __global__ void __launch_bounds__(TB) region_kernel(const float* __restrict__ pred, float* __restrict__ gt, int H, int W,
                                                     int binarize, double* __restrict__ acc) {
   long X, Y;
-  centroid(acc, H, W, X, Y);
+  centroid(acc[A_N1], acc[A_CX], acc[A_CY], H, W, X, Y);
   const long N = (long)H * W;
   const double ysum = acc[A_YSUM];
   const bool special = ysum == 0.0 || ysum == (double)N;   // y == 0 / y == 1: no binarisation
-  double v[24];
-#pragma unroll
-  for (int j = 0; j < 24; j++) v[j] = 0.0;
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+  double v[24] = {};
+  SWEEP(i, N) {
     const long y = i / W, x = i - y * W;
     const float m = gt[i];
     const double p = pred[i], mb = m >= 0.5f ? 1.0 : 0.0;
-    const int q = (y < Y ? 0 : 2) + (x < X ? 0 : 1);     // LT, RT, LB, RB
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k == q) {
-        v[6 * k + 0] += 1.0; v[6 * k + 1] += p; v[6 * k + 2] += mb;
-        v[6 * k + 3] += p * p; v[6 * k + 4] += mb * mb; v[6 * k + 5] += p * mb;
-      }
-    }
+    const double t[6] = {1.0, p, mb, p * p, mb * mb, p * mb};
+    QUAD_ADD(v, quadrant(x, y, X, Y), t);
     if (binarize && !special) gt[i] = m >= 0.5f ? 1.f : 0.f;
   }
-  int slot[24];
-#pragma unroll
-  for (int j = 0; j < 24; j++) slot[j] = Q_OFF + j;
-  block_add<24>(v, acc, slot);
+  block_add(v, acc + Q_OFF);
 }
 
 // nearest foreground row in each column (scipy's first-axis pass; ties -> lower row).  One thread
@@ -254,7 +265,7 @@ __global__ void __launch_bounds__(64) edt_row_kernel(const int* __restrict__ fea
 
 __global__ void __launch_bounds__(TB) wf_et_kernel(const float* __restrict__ pred, const float* __restrict__ gt, long N,
                                                    const int* __restrict__ idx, float* __restrict__ et) {
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+  SWEEP(i, N) {
     const bool g = gt[i] >= 0.5f;
     float e;
     if (g) {
@@ -275,10 +286,10 @@ __global__ void __launch_bounds__(TB) wf_sum_kernel(const float* __restrict__ pr
   __syncthreads();
   const long N = (long)H * W;
   const double c5 = log(0.5) / 5.0;
-  double v[2] = {0.0, 0.0};
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+  double v[2] = {0.0, 0.0};                        // A_EWFG, A_EWBG
+  SWEEP(i, N) {
     const long y = i / W, x = i - y * W;
-    double s = 0.0;                                // scipy.ndimage.convolve(mode="constant", cval=0)
+    double s = 0.0;                               // scipy.ndimage.convolve(mode="constant", cval=0)
     for (int dy = -3; dy <= 3; dy++) {
       const long yy = y + dy;
       if (yy < 0 || yy >= H) continue;
@@ -295,8 +306,7 @@ __global__ void __launch_bounds__(TB) wf_sum_kernel(const float* __restrict__ pr
     if (g) v[0] += (double)mn;
     else v[1] += (double)mn * (2.0 - exp(c5 * sqrt((double)d2[i])));
   }
-  const int slot[2] = {A_EWFG, A_EWBG};
-  block_add<2>(v, acc, slot);
+  block_add(v, acc + A_EWFG);
 }
 
 DEV float fsc(float prec, float rec) {            // (1 + 0.3) * prec * recall / (0.3 * prec + recall), f32 ops
@@ -326,6 +336,29 @@ DEV double o_score(double n, double s1, double s2) {   // _object: 2x / (x^2 + 1
   return 2.0 * x / (x * x + 1.0 + sd + 1e-20);
 }
 
+// the sums of one (pred, mask) pair that the S-measure takes besides its quadrant moments: raw sums of mask and pred,
+// then of the binarised mask its count, the object moments of pred on / off it and its centroid moments
+struct PairSums {
+  double ysum, psum, n1, fg1, fg2, bg1, bg2, cx, cy;
+};
+
+// S-measure (metrics.py:257-272, 329-356) of one pair; q holds the four quadrants' [n, sp, sm, spp, smm, spm]
+DEV double s_measure(const PairSums& s, const double* q, int H, int W) {
+  const double Nd = (double)H * W;
+  const double y = s.ysum / Nd, xm = s.psum / Nd;
+  if (y == 0.0) return 1.0 - xm;
+  if (y == 1.0) return xm;
+  const double n0 = Nd - s.n1, u = s.n1 / Nd;
+  const double so = u * o_score(s.n1, s.fg1, s.fg2) + (1 - u) * o_score(n0, s.bg1, s.bg2);
+  long X, Y;
+  centroid(s.n1, s.cx, s.cy, H, W, X, Y);
+  const double w1 = (double)X * Y / Nd, w2 = (double)(W - X) * Y / Nd, w3 = (double)X * (H - Y) / Nd;
+  const double w4 = 1 - w1 - w2 - w3;
+  const double sr = w1 * q_ssim(q) + w2 * q_ssim(q + 6) + w3 * q_ssim(q + 12) + w4 * q_ssim(q + 18);
+  const double S = 0.5 * so + 0.5 * sr;
+  return S < 0 ? 0.0 : S;
+}
+
 __global__ void __launch_bounds__(256) final_kernel(const double* __restrict__ acc, int H, int W, int sm_only,
                                                     double* __restrict__ out) {
   __shared__ double red[256];
@@ -335,27 +368,8 @@ __global__ void __launch_bounds__(256) final_kernel(const double* __restrict__ a
   const double Nd = (double)N;
   const unsigned long long* acc_u = (const unsigned long long*)acc;
   // ---- S-measure (every thread computes it; thread 0 writes)
-  double S;
-  {
-    const double y = acc[A_YSUM] / Nd, xm = acc[A_PSUM] / Nd;
-    if (y == 0.0) S = 1.0 - xm;
-    else if (y == 1.0) S = xm;
-    else {
-      const double n1 = acc[A_N1], n0 = Nd - n1, u = n1 / Nd;
-      const double ofg = o_score(n1, acc[A_FG1], acc[A_FG2]);
-      const double obg = o_score(n0, acc[A_BG1], acc[A_BG2]);
-      const double so = u * ofg + (1 - u) * obg;
-      long X, Y;
-      centroid(acc, H, W, X, Y);
-      const double area = Nd;
-      const double w1 = (double)X * Y / area, w2 = (double)(W - X) * Y / area, w3 = (double)X * (H - Y) / area;
-      const double w4 = 1 - w1 - w2 - w3;
-      const double* q = acc + Q_OFF;
-      const double sr = w1 * q_ssim(q) + w2 * q_ssim(q + 6) + w3 * q_ssim(q + 12) + w4 * q_ssim(q + 18);
-      S = 0.5 * so + 0.5 * sr;
-      if (S < 0) S = 0.0;
-    }
-  }
+  const PairSums ps = {acc[A_YSUM], acc[A_PSUM], acc[A_N1], acc[A_FG1], acc[A_FG2], acc[A_BG1], acc[A_BG2], acc[A_CX], acc[A_CY]};
+  const double S = s_measure(ps, acc + Q_OFF, H, W);
   if (sm_only) {
     if (t == 0) { out[0] = 0; out[1] = 0; out[2] = 0; out[3] = S; out[4] = 0; out[5] = 0; }
     return;
@@ -460,105 +474,52 @@ constexpr int FQ_B = FQ_G + 32;
 constexpr int FQ_N = 32 + 20;
 constexpr int F_WORDS = 96;
 
-__global__ void __launch_bounds__(TB) flip_stats_kernel(const float* __restrict__ a, const float* __restrict__ bm,
-                                                        const float* __restrict__ gt, long N, int W, float thr,
-                                                        double* __restrict__ acc) {
-  double v[F_NS1];
-#pragma unroll
-  for (int j = 0; j < F_NS1; j++) v[j] = 0.0;
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+// 4 waves per SIMD: the 2048 blocks of sweep_grid then run as two full rounds of 1024.  At the 6 waves its 80 VGPRs
+// would allow, the rounds are 1536 + 512 blocks, the second on a third of the wave slots, and the kernel measured
+// 64 us against 58 us at 1536 x 2048 (metrics kernels)
+__global__ void __launch_bounds__(TB) __attribute__((amdgpu_waves_per_eu(4, 4)))
+flip_stats_kernel(const float* __restrict__ a, const float* __restrict__ bm, const float* __restrict__ gt, long N, int W,
+                  float thr, double* __restrict__ acc) {
+  double v[F_NS1] = {};
+  SWEEP(i, N) {
     const long y = i / W, x = i - y * W;
     const float pa = a[i], pb = bm[i + (W - 1 - 2 * x)], m = gt[i];     // b(y, x) = bm[y][W - 1 - x]
-    const double ad = pa, bd = pb;
-    const double qa = (double)(1.f - pa), qb = (double)(1.f - pb);      // bg = 1 - pred in float32, as stats_kernel
-    v[F_YSUM] += (double)m; v[F_ASUM] += ad; v[F_BSUM] += bd;
-    if (m >= 0.5f) {
-      v[F_N1] += 1.0; v[F_CX] += (double)x; v[F_CY] += (double)y;
-      v[F_AFG1] += ad; v[F_AFG2] += ad * ad; v[F_BFG1] += bd; v[F_BFG2] += bd * bd;
-    } else {
-      v[F_ABG1] += qa; v[F_ABG2] += qa * qa; v[F_BBG1] += qb; v[F_BBG2] += qb * qb;
-    }
-    if (pb >= 0.5f) {
-      v[F_NB1] += 1.0; v[F_BCX] += (double)x; v[F_BCY] += (double)y;
-      v[F_CFG1] += ad; v[F_CFG2] += ad * ad;
-    } else {
-      v[F_CBG1] += qa; v[F_CBG2] += qa * qa;
-    }
+    v[F_YSUM] += (double)m; v[F_ASUM] += (double)pa; v[F_BSUM] += (double)pb;
+    if (m >= 0.5f) { v[F_N1] += 1.0; v[F_CX] += (double)x; v[F_CY] += (double)y; }
+    OBJ_ADD(v + F_AFG1, m >= 0.5f, pa);
+    OBJ_ADD(v + F_BFG1, m >= 0.5f, pb);
+    if (pb >= 0.5f) { v[F_NB1] += 1.0; v[F_BCX] += (double)x; v[F_BCY] += (double)y; }
+    OBJ_ADD(v + F_CFG1, pb >= 0.5f, pa);
     const bool ta = pa > thr, tb = pb > thr, tg = m > 0.5f;              // calculate_iou's binarisation
     v[F_I_AG] += (ta && tg) ? 1.0 : 0.0; v[F_U_AG] += (ta || tg) ? 1.0 : 0.0;
     v[F_I_BG] += (tb && tg) ? 1.0 : 0.0; v[F_U_BG] += (tb || tg) ? 1.0 : 0.0;
     v[F_I_AB] += (ta && tb) ? 1.0 : 0.0; v[F_U_AB] += (ta || tb) ? 1.0 : 0.0;
   }
-  int slot[F_NS1];
-#pragma unroll
-  for (int j = 0; j < F_NS1; j++) slot[j] = j;
-  block_add<F_NS1>(v, acc, slot);
-}
-
-// the two centroids: of gt >= 0.5 (pairs 1 and 2) and of b >= 0.5 (pair 3)
-DEV void flip_centroids(const double* acc, int H, int W, long& X, long& Y, long& XB, long& YB) {
-  double c[A_NSCAL];
-  c[A_N1] = acc[F_N1]; c[A_CX] = acc[F_CX]; c[A_CY] = acc[F_CY];
-  centroid(c, H, W, X, Y);
-  c[A_N1] = acc[F_NB1]; c[A_CX] = acc[F_BCX]; c[A_CY] = acc[F_BCY];
-  centroid(c, H, W, XB, YB);
+  block_add(v, acc);
 }
 
 __global__ void __launch_bounds__(TB) flip_region_kernel(const float* __restrict__ a, const float* __restrict__ bm,
                                                          const float* __restrict__ gt, int H, int W, double* __restrict__ acc) {
-  long X, Y, XB, YB;
-  flip_centroids(acc, H, W, X, Y, XB, YB);
+  long X, Y, XB, YB;       // the centroids of gt >= 0.5 (pairs 1 and 2) and of b >= 0.5 (pair 3)
+  centroid(acc[F_N1], acc[F_CX], acc[F_CY], H, W, X, Y);
+  centroid(acc[F_NB1], acc[F_BCX], acc[F_BCY], H, W, XB, YB);
   const long N = (long)H * W;
-  double v[FQ_N];
-#pragma unroll
-  for (int j = 0; j < FQ_N; j++) v[j] = 0.0;
-  for (long i = blockIdx.x * (long)TB + threadIdx.x; i < N; i += (long)gridDim.x * TB) {
+  double v[FQ_N] = {};
+  SWEEP(i, N) {
     const long y = i / W, x = i - y * W;
     const float pb = bm[i + (W - 1 - 2 * x)];
     const double ad = a[i], bd = pb;
     const double mg = gt[i] >= 0.5f ? 1.0 : 0.0, mb = pb >= 0.5f ? 1.0 : 0.0;
-    const int q = (y < Y ? 0 : 2) + (x < X ? 0 : 1);       // LT, RT, LB, RB
-    const int qb = (y < YB ? 0 : 2) + (x < XB ? 0 : 1);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k == q) {
-        v[8 * k + 0] += 1.0; v[8 * k + 1] += mg;
-        v[8 * k + 2] += ad; v[8 * k + 3] += ad * ad; v[8 * k + 4] += ad * mg;
-        v[8 * k + 5] += bd; v[8 * k + 6] += bd * bd; v[8 * k + 7] += bd * mg;
-      }
-      if (k == qb) {
-        v[32 + 5 * k + 0] += 1.0; v[32 + 5 * k + 1] += mb;
-        v[32 + 5 * k + 2] += ad; v[32 + 5 * k + 3] += ad * ad; v[32 + 5 * k + 4] += ad * mb;
-      }
-    }
+    const double tg[8] = {1.0, mg, ad, ad * ad, ad * mg, bd, bd * bd, bd * mg};
+    const double tb[5] = {1.0, mb, ad, ad * ad, ad * mb};
+    QUAD_ADD(v, quadrant(x, y, X, Y), tg);
+    QUAD_ADD(v + (FQ_B - FQ_G), quadrant(x, y, XB, YB), tb);
   }
-  int slot[FQ_N];
-#pragma unroll
-  for (int j = 0; j < FQ_N; j++) slot[j] = FQ_G + j;
-  block_add<FQ_N>(v, acc, slot);
-}
-
-// S of one (pred, mask) pair from its sums, as final_kernel states it: ymean decides the special cases, q holds the
-// four quadrants' [n, sp, sm, spp, smm, spm]
-DEV double flip_s(double ymean, double xmean, double n1, double fg1, double fg2, double bg1, double bg2, long X, long Y,
-                  const double* q, int H, int W) {
-  if (ymean == 0.0) return 1.0 - xmean;
-  if (ymean == 1.0) return xmean;
-  const double Nd = (double)H * W, n0 = Nd - n1, u = n1 / Nd;
-  const double so = u * o_score(n1, fg1, fg2) + (1 - u) * o_score(n0, bg1, bg2);
-  const double w1 = (double)X * Y / Nd, w2 = (double)(W - X) * Y / Nd, w3 = (double)X * (H - Y) / Nd;
-  const double w4 = 1 - w1 - w2 - w3;
-  const double sr = w1 * q_ssim(q) + w2 * q_ssim(q + 6) + w3 * q_ssim(q + 12) + w4 * q_ssim(q + 18);
-  double S = 0.5 * so + 0.5 * sr;
-  if (S < 0) S = 0.0;
-  return S;
+  block_add(v, acc + FQ_G);
 }
 
 __global__ void flip_final_kernel(const double* __restrict__ acc, int H, int W, double* __restrict__ out) {
   if (threadIdx.x != 0) return;
-  const double Nd = (double)H * W;
-  long X, Y, XB, YB;
-  flip_centroids(acc, H, W, X, Y, XB, YB);
   double q1[24], q2[24], q3[24];
   for (int k = 0; k < 4; k++) {
     const double* g = acc + FQ_G + 8 * k;
@@ -568,31 +529,45 @@ __global__ void flip_final_kernel(const double* __restrict__ acc, int H, int W, 
     const double r3[6] = {b[0], b[2], b[1], b[3], b[1], b[4]};     // a vs m
     for (int j = 0; j < 6; j++) { q1[6 * k + j] = r1[j]; q2[6 * k + j] = r2[j]; q3[6 * k + j] = r3[j]; }
   }
-  const double ysum = acc[F_YSUM], n1 = acc[F_N1], nb1 = acc[F_NB1];
+  const double ysum = acc[F_YSUM], n1 = acc[F_N1];
   // step 1 binarises gt in place unless its raw mean is 0 or 1 (region_kernel's `special`); step 2 then sees the
-  // binarised plane, whose mean is n1 / N
-  const bool special = ysum == 0.0 || ysum == Nd;
-  const double am = acc[F_ASUM] / Nd, bmean = acc[F_BSUM] / Nd;
-  out[0] = flip_s(ysum / Nd, am, n1, acc[F_AFG1], acc[F_AFG2], acc[F_ABG1], acc[F_ABG2], X, Y, q1, H, W);
-  out[1] = flip_s(special ? ysum / Nd : n1 / Nd, bmean, n1, acc[F_BFG1], acc[F_BFG2], acc[F_BBG1], acc[F_BBG2], X, Y, q2, H, W);
-  out[2] = flip_s(bmean, am, nb1, acc[F_CFG1], acc[F_CFG2], acc[F_CBG1], acc[F_CBG2], XB, YB, q3, H, W);
+  // binarised plane, whose sum is n1
+  const bool special = ysum == 0.0 || ysum == (double)H * W;
+  const PairSums p1 = {ysum, acc[F_ASUM], n1, acc[F_AFG1], acc[F_AFG2], acc[F_ABG1], acc[F_ABG2], acc[F_CX], acc[F_CY]};
+  const PairSums p2 = {special ? ysum : n1, acc[F_BSUM], n1, acc[F_BFG1], acc[F_BFG2], acc[F_BBG1], acc[F_BBG2], acc[F_CX], acc[F_CY]};
+  const PairSums p3 = {acc[F_BSUM], acc[F_ASUM], acc[F_NB1], acc[F_CFG1], acc[F_CFG2], acc[F_CBG1], acc[F_CBG2], acc[F_BCX], acc[F_BCY]};
+  out[0] = s_measure(p1, q1, H, W);
+  out[1] = s_measure(p2, q2, H, W);
+  out[2] = s_measure(p3, q3, H, W);
   for (int j = 0; j < 6; j++) out[3 + j] = acc[F_I_AG + j];
 }
+
+// s3od_eval_metrics' workspace for an H x W image: the accumulators, four planes and, for rows too wide for
+// edt_row_kernel's LDS, two planes of envelope scratch.  ws may be null when only `bytes` is wanted.
+struct EvalWs {
+  long bytes = 0;
+  double* acc;
+  int *feat, *idx, *d2;
+  float* et;
+  int *sx, *sd;
+  EvalWs(int H, int W, void* ws) {
+    const long plane = (long)H * W * 4, env = W > EDT_LDS_W ? plane : 0;
+    auto take = [&](long n) { char* p = ws ? (char*)ws + bytes : nullptr; bytes += n; return p; };
+    acc = (double*)take((long)ACC_WORDS * 8);
+    feat = (int*)take(plane); idx = (int*)take(plane); d2 = (int*)take(plane);
+    et = (float*)take(plane);
+    sx = (int*)take(env); sd = (int*)take(env);
+  }
+};
 
 }  // namespace
 
 extern "C" {
 
-static long ws_bytes_for(int H, int W) {
-  const long N = (long)H * W;
-  return (long)ACC_WORDS * 8 + N * 4 /*feat*/ + N * 4 /*idx*/ + N * 4 /*d2*/ + N * 4 /*et*/ +
-         (W > EDT_LDS_W ? N * 8 : 0) /*envelope scratch*/;
-}
-
 // *bytes (host) = scratch s3od_eval_metrics needs for an H x W image
 int s3od_eval_metrics_ws(int H, int W, long* bytes) {
   S3OD_REQUIRE(bytes && H > 0 && W > 0, "eval_metrics_ws: bad arguments");
-  *bytes = ws_bytes_for(H, W);
+  *bytes = EvalWs(H, W, nullptr).bytes;
   return 0;
 }
 
@@ -606,31 +581,25 @@ int s3od_eval_metrics(const float* pred, float* gt, int H, int W, const float* t
                       int sm_only, int binarize, double* out, void* stream) {
   S3OD_REQUIRE(pred && gt && ws && out && thr && k7, "eval_metrics: null pointer");
   S3OD_REQUIRE(H >= 2 && W >= 2 && H <= 32768 && W <= 32768, "eval_metrics: image must be 2..32768 on each side");
-  S3OD_REQUIRE(ws_bytes >= ws_bytes_for(H, W), "eval_metrics: workspace too small");
+  const EvalWs w(H, W, ws);
+  S3OD_REQUIRE(ws_bytes >= w.bytes, "eval_metrics: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const long N = (long)H * W;
   Tables T;
   for (int i = 0; i < NT; i++) T.thr[i] = thr[i];
   for (int i = 0; i < 49; i++) T.k7[i] = k7[i];
-  char* w = (char*)ws;
-  double* acc = (double*)w;
-  int* feat = (int*)(w + (long)ACC_WORDS * 8);
-  int* idx = feat + N;
-  int* d2 = idx + N;
-  float* et = (float*)(d2 + N);
-  int* sx = (int*)(et + N);
-  int* sd = sx + (W > EDT_LDS_W ? N : 0);
+  double* acc = w.acc;
   hipError_t e = hipMemsetAsync(acc, 0, (size_t)ACC_WORDS * 8, st);
   if (e != hipSuccess) return (int)e;
   const int g = sweep_grid(N);
   hipLaunchKernelGGL(stats_kernel, dim3(g), dim3(TB), 0, st, pred, (const float*)gt, N, W, T, sm_only, acc);
   if (!sm_only) {
     // the distance transform reads gt before region_kernel may binarise it (same foreground either way)
-    hipLaunchKernelGGL(edt_col_kernel, dim3(cdiv(W, 64)), dim3(64), 0, st, (const float*)gt, H, W, feat);
-    hipLaunchKernelGGL(edt_row_kernel, dim3(H), dim3(64), 0, st, (const int*)feat, H, W, idx, d2, sx, sd);
-    hipLaunchKernelGGL(wf_et_kernel, dim3(g), dim3(TB), 0, st, pred, (const float*)gt, N, (const int*)idx, et);
-    hipLaunchKernelGGL(wf_sum_kernel, dim3(g), dim3(TB), 0, st, pred, (const float*)gt, H, W, (const float*)et,
-                       (const int*)d2, T, acc);
+    hipLaunchKernelGGL(edt_col_kernel, dim3(cdiv(W, 64)), dim3(64), 0, st, (const float*)gt, H, W, w.feat);
+    hipLaunchKernelGGL(edt_row_kernel, dim3(H), dim3(64), 0, st, (const int*)w.feat, H, W, w.idx, w.d2, w.sx, w.sd);
+    hipLaunchKernelGGL(wf_et_kernel, dim3(g), dim3(TB), 0, st, pred, (const float*)gt, N, (const int*)w.idx, w.et);
+    hipLaunchKernelGGL(wf_sum_kernel, dim3(g), dim3(TB), 0, st, pred, (const float*)gt, H, W, (const float*)w.et,
+                       (const int*)w.d2, T, acc);
   }
   hipLaunchKernelGGL(region_kernel, dim3(g), dim3(TB), 0, st, pred, gt, H, W, binarize, acc);
   hipLaunchKernelGGL(final_kernel, dim3(1), dim3(256), 0, st, (const double*)acc, H, W, sm_only, out);

@@ -138,9 +138,9 @@ def test_flip_scores_golden(name):
 
 
 # ---------------------------------------------------------------------------------- 3. vs the existing path
-def _big_case():
-    """1024 x 1000: more pixels than 2048 blocks x 256 threads, so the grid-stride loop and every block's atomics run."""
-    H, W = 1024, 1000
+def _big_case(H=1024, W=1000):
+    """1024 x 1000: more pixels than 2048 blocks x 256 threads, so the grid-stride loop and every block's atomics run.
+    Scaled down: 3 x 85 and 16 x 16 fill one block, 3 x 86 puts two live threads into a second one."""
     r = np.random.default_rng(31)
     g = np.maximum(blob_gt(H, W, 32), blob_gt(H, W, 33))
     a = (0.45 * g + 0.55 * r.random((H, W))).astype(np.float32)
@@ -148,15 +148,26 @@ def _big_case():
     return tuple(torch.from_numpy(t).cuda() for t in (a, bm, (0.8 * g + 0.1).astype(np.float32)))
 
 
-@pytest.mark.parametrize("name", NAMES + ["big_1024x1000"])
+SOFT = {"big_1024x1000": (1024, 1000), "soft_3x85": (3, 85), "soft_16x16": (16, 16), "soft_3x86": (3, 86)}
+
+
+@pytest.mark.parametrize("name", NAMES + list(SOFT))
 def test_flip_scores_vs_existing_path(name):
     from s3od_amd.flip_scores import flip_scores_out
-    a, bm, gt = _big_case() if name == "big_1024x1000" else _case(name)
+    a, bm, gt = _big_case(*SOFT[name]) if name in SOFT else _case(name)
     v = flip_scores_out(a, bm, gt).cpu().numpy()
     want = existing_path(a, bm, gt)
     print(f"{name}: S {v[:3]} existing {want[:3]} max err {s_err(v[:3], want[:3]):.3g}")
     assert same_s(v[:3], want[:3]), (v[:3], want[:3])
     assert np.array_equal(v[3:], want[3:]), (v[3:], want[3:])
+
+
+def test_flip_scores_repeat_bit_for_bit_in_one_block():
+    """16 x 16 is one block: no two partial sums meet in an atomic, so a second call repeats every bit."""
+    from s3od_amd.flip_scores import flip_scores_out
+    a, bm, gt = _big_case(16, 16)
+    v = [flip_scores_out(a.clone(), bm.clone(), gt.clone()).cpu().numpy() for _ in range(2)]
+    assert v[0].tobytes() == v[1].tobytes(), v
 
 
 def test_flip_scores_rejects():

@@ -43,10 +43,10 @@ PRODUCTION = [
 NO_SGPR_SPILL = [r"^void conv3x3_c64_rw_kernel<(0|2), 64, 2>"]
 
 
-def _kernels():
-    """{(mangled, demangled name): (private_segment_fixed_size, sgpr_spill_count, vgpr_spill_count)} over build/*.o."""
+def _kernels(objs="*.o"):
+    """{(mangled, demangled name): (private_segment_fixed_size, sgpr_spill_count, vgpr_spill_count)} over build/<objs>."""
     out = {}
-    for obj in sorted((ROOT / "build").glob("*.o")):
+    for obj in sorted((ROOT / "build").glob(objs)):
         tmp = ROOT / "build" / f".{obj.stem}.fatbin"
         co = ROOT / "build" / f".{obj.stem}.co"
         if subprocess.run([TOOLS[0], "-O", "binary", "--only-section=.hip_fatbin", str(obj), str(tmp)],
@@ -105,3 +105,13 @@ def test_grouped_masked_dgrad_is_not_built(kernels):
     """The grouped masked data-gradient instances (mode 1, GB 2 / 4) and every GB-4 instance are gone."""
     gone = [n for _, n in kernels if re.search(r"^void conv3x3_c64_rw_kernel<(1, \d+, [24]|\d, \d+, 4)>", n)]
     assert not gone, gone
+
+
+def test_metrics_kernels_have_no_private_memory(kernels):
+    """The sweeps of metrics.hip keep up to 52 float64 partial sums per thread, and whatever they index at run time
+    goes to private memory: a table of accumulator slots indexed by the thread once cost flip_region_kernel 224
+    bytes of scratch per lane, a per-pixel update inlined from a function 432."""
+    mine = _kernels("metrics.o")
+    assert len(mine) == 10, sorted(n for _, n in mine)
+    bad = [f"{name[:120]}: private {priv} B, {vgpr} VGPR spills" for (_, name), (priv, _, vgpr) in mine.items() if priv or vgpr]
+    assert not bad, "\n".join(bad)

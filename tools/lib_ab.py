@@ -14,7 +14,8 @@ shapes and at the training step's shapes: give the first build twice, `glue pare
 third is judged by whether the first two agree bit for bit -- then it must too -- or only to summation order, as the sums
 through fp32 atomics do -- then rel-L2 1e-5, or the first two's own scatter where that is larger; the training
 shapes are also timed);
-augment (the entries of data_ops.hip, `augment parent parent new` like glue: see augment()).
+augment (the entries of data_ops.hip, `augment parent parent new` like glue: see augment());
+metrics (s3od_eval_metrics and s3od_flip_scores, `metrics parent parent new`: see metrics()).
 """
 import ctypes
 import os
@@ -561,6 +562,110 @@ def augment(libs, rounds):
     return bad + slow
 
 
+def metrics(libs, rounds):
+    """The entries of metrics.hip, `metrics parent parent new`: s3od_eval_metrics (full with binarize 0 and 1 on a binary gt,
+    sm_only with binarize 0 and 1 on a soft gt: out[6] and the gt plane it leaves) and s3od_flip_scores (out[9], soft gt) at
+    3x85 and 16x16 (one block), 3x86 (two live threads in a second block), 65x63, 1024x1000 (a second trip of the
+    grid-stride loop) and 1536x2048, 10 calls per build and entry on the same buffers.  Per output number: the sums of
+    integers (MaxF with a binary gt, the six IoU counts) equal the first build's bit for bit; where all 20 numbers of the
+    first two builds are one value the third's are that value; elsewhere (float64 atomics of many blocks) the third's
+    largest distance from the first two's mean is at most 4x their spread (max - min: 10 calls undersample the orders of up
+    to 2048 blocks' atomics) and inside the bound tests/test_gpu_metrics.py and test_gpu_flip_scores.py hold against the
+    reference.  Timed at 1024x1000, 1536x2048 and 1024^2: full eval, three sm_only steps, one flip score; the third build's
+    median must not lie above the first two's max + (max - min)."""
+    import numpy as np
+    from s3od_amd.metrics import _K7, _THR
+    CALLS = 10
+    TOL = [1e-9, 2e-7, 2e-6, 2e-6, 1e-9, 1e-9]               # tests/test_gpu_metrics.py, relative to max(1, |value|)
+    KEYS = ("mae", "max_f", "avg_f", "s", "em", "wfm")
+    FKEYS = ("s_ag", "s_bg", "s_ab", "i_ag", "u_ag", "i_bg", "u_bg", "i_ab", "u_ab")
+    st = stream()
+    bad = slow = 0
+
+    def planes(H, W):
+        g = torch.Generator(device="cuda").manual_seed(1000 * H + W)
+        u = lambda: torch.rand(H, W, device="cuda", generator=g)
+        gb = (u() < 0.4).float()
+        a, b = (0.7 * gb + 0.3 * u()).clamp(0, 1), (0.6 * gb + 0.4 * u()).clamp(0, 1)
+        return a, b, torch.flip(b, [1]).contiguous(), gb, 0.8 * gb + 0.1
+
+    def workspace(H, W):
+        nb = ctypes.c_long(0)
+        libs[0]("s3od_eval_metrics_ws", H, W, ctypes.addressof(nb))
+        return torch.empty(nb.value, dtype=torch.uint8, device="cuda")
+
+    def judge(tag, keys, exact, tol, vals):
+        """vals[build][call] = float64 outputs -> report lines; exact: indices that are sums of integers"""
+        nonlocal bad
+        bits = lambda x: np.asarray(x, np.float64).view(np.int64)
+        for k, key in enumerate(keys):
+            par = np.array([v[k] for b in vals[:2] for v in b])
+            new = np.array([v[k] for v in vals[2]]) if len(vals) == 3 else par
+            fixed = len(set(bits(par).tolist())) == 1
+            if fixed or k in exact:
+                ok = bool(np.all(bits(new) == bits(par)[0])) and (fixed or k not in exact)
+                line = f"  {tag} {key}: parents {'one value' if fixed else 'DIFFER'} {float(par[0])!r}, new {'equal' if ok else f'DIFFERS by up to {float(np.abs(new - par[0]).max()):.3g}'}"
+            else:
+                spread, dev = float(par.max() - par.min()), float(np.abs(new - par.mean()).max())
+                ok = dev <= 4 * spread and dev <= tol[k] * max(1.0, abs(par.mean()))
+                line = f"  {tag} {key}: parents' spread {spread:.3g} about {float(par.mean())!r}, new deviates {dev:.3g} (bound {tol[k] * max(1.0, abs(par.mean())):.1g})"
+            print(line + ("" if ok else " <-- MISS"), flush=True)
+            bad += not ok
+
+    def bench(tag, fns):
+        nonlocal slow
+        ts = [[] for _ in libs]
+        for r in range(max(rounds, 5)):
+            for i in [(r + j) % len(libs) for j in range(len(libs))]:
+                ts[i].append(timed(fns[i], 20) * 1e3)
+        med = [sorted(t)[len(t) // 2] for t in ts]
+        line = f"  timed {tag}: us " + " | ".join(f"lib{i} med {m:8.1f} ({min(t):8.1f} .. {max(t):8.1f})" for i, (m, t) in enumerate(zip(med, ts)))
+        if len(libs) == 3:
+            lo, hi = min(ts[0] + ts[1]), max(ts[0] + ts[1])
+            verdict = "below" if med[2] < lo else "within" if med[2] <= hi else "within the widened range" if med[2] <= hi + (hi - lo) else "ABOVE"
+            line += f" | parents' range {lo:.1f} .. {hi:.1f}: new median {verdict}"
+            slow += verdict == "ABOVE"
+        print(line, flush=True)
+
+    for H, W in ((3, 85), (16, 16), (3, 86), (65, 63), (1024, 1000), (1536, 2048), (1024, 1024)):
+        a, b, bm, gbin, gsoft = planes(H, W)
+        ws, out6, out9 = workspace(H, W), torch.empty(6, dtype=torch.float64, device="cuda"), torch.empty(9, dtype=torch.float64, device="cuda")
+        fws = torch.empty(128, dtype=torch.float64, device="cuda")
+        gt = torch.empty_like(gbin)
+        ev = lambda L, p, g, sm, bz: L("s3od_eval_metrics", p, g, H, W, _THR.ctypes.data, _K7.ctypes.data, ws, ws.numel(), sm, bz, out6, st)
+        fl = lambda L: L("s3od_flip_scores", a, bm, gsoft, H, W, 0.5, fws, fws.numel() * 8, out9, st)
+        print(f"{H}x{W} ({-(-H * W // 256)} blocks of 256 pixels, at most 2048 run):", flush=True)
+        if (H, W) != (1024, 1024):                                        # (1024^2 is timed only)
+            for sm, g0, bz in ((0, gbin, 1), (0, gbin, 0), (1, gsoft, 1), (1, gsoft, 0)):
+                vals, left = [[] for _ in libs], []
+                for _ in range(CALLS):
+                    for i, L in enumerate(libs):
+                        gt.copy_(g0)
+                        ev(L, a, gt, sm, bz)
+                        vals[i].append(out6.cpu().numpy())
+                        left.append(gt.clone())
+                tag = f"eval {'sm_only' if sm else 'full'} binarize {bz}"
+                judge(tag, KEYS, {1} if not sm else set(), TOL, vals)
+                same = all(torch.equal(t, left[0]) for t in left)
+                print(f"  {tag} gt plane left behind: {'equal in every call' if same else 'DIFFERS <-- MISS'}", flush=True)
+                bad += not same
+            vals = [[] for _ in libs]
+            for _ in range(CALLS):
+                for i, L in enumerate(libs):
+                    fl(L)
+                    vals[i].append(out9.cpu().numpy())
+            judge("flip", FKEYS, set(range(3, 9)), [2e-6] * 9, vals)
+        if H * W >= 1024 * 1000:
+            gt.copy_(gbin)
+            b3 = b.clone()                                               # step 3's mask: binarised in place by the first call
+            bench("full eval, binary gt", [lambda L=L: ev(L, a, gt, 0, 1) for L in libs])
+            bench("three sm_only steps", [lambda L=L: (ev(L, a, gt, 1, 1), ev(L, b, gt, 1, 1), ev(L, a, b3, 1, 1)) for L in libs])
+            bench("one flip score", [lambda L=L: fl(L) for L in libs])
+    print(f"metrics: {bad} outputs MISS the rule, {slow} timed entries with the last build's median above the first two's "
+          f"range widened by its width")
+    return bad + slow
+
+
 if __name__ == "__main__":
     what, paths = sys.argv[1], sys.argv[2:]
     libs = [Lib(p) for p in paths]
@@ -575,3 +680,5 @@ if __name__ == "__main__":
         sys.exit(1 if glue(libs, rounds) else 0)
     elif what == "augment":
         sys.exit(1 if augment(libs, rounds) else 0)
+    elif what == "metrics":
+        sys.exit(1 if metrics(libs, rounds) else 0)
